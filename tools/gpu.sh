@@ -18,7 +18,7 @@
 #                                      on frozen trained-density steps
 #   fbench_ab TAG [fbench args]        composite A/B by fbench + kernel trace
 #   shared_ranks TAG                   N = 1, 2, 4 bench ranks sharing one GPU (gloo)
-#   final TAG                          bench.py (full) + rocprofv3 kernel trace of the bench
+#   final TAG                          bench.py --full + rocprofv3 kernel trace of the bench
 #   alpha_ab TAG [KNOB ['V1 V2']]      alpha path A/B (default knob 9: backward DPP vs shuffle sums;
 #                                      knob 18 = 100000: forward without lane-group lists),
 #                                      interleaved twice
@@ -124,15 +124,15 @@ fbench_ab)
   run fbench 300 python tools/fbench.py "$@"
   run trace 300 rocprofv3 --kernel-trace --stats -d "$OUT/tr" -o t --output-format csv -- python3 tools/fbench.py "$@" ;;
 shared_ranks)
-  run n1 300 python bench.py --no-cpu --no-secondary
+  run n1 300 python bench.py --full --no-cpu --no-secondary
   for n in 2 4; do
-    GSVC_BENCH_SHARED_GPU=1 run n$n 400 python bench.py --gpus $n --backend gloo --no-cpu
+    GSVC_BENCH_SHARED_GPU=1 run n$n 400 python bench.py --full --gpus $n --backend gloo --no-cpu
   done ;;
 final)
   # the round's bench line (with the CPU baselines) and the kernel trace of the
   # same workload (the bench without its CPU legs), for profiles/rNN/final
-  run bench 900 python bench.py
-  run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o b --output-format csv -- python3 bench.py --no-cpu ;;
+  run bench 900 python bench.py --full
+  run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o b --output-format csv -- python3 bench.py --full --no-cpu ;;
 alpha_ab)
   KN=${1:-9}; VALS=${2:-"0 1"}
   for rep in 1 2; do
