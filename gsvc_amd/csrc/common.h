@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/gsvc_amd.h"
+#include "../../include/gsvc_amd_diag.h"  // enum gsvc_knob
 
 namespace gsvc {
 
@@ -64,16 +65,18 @@ int dev_copy(void *dst, const void *src, size_t bytes, hipStream_t s);
 // for tools/ and the variant-comparison tests).  In the product library every
 // knob is the constant 0 -- the production choice -- and the diagnostic
 // variants are not compiled (``if constexpr (kDiag)`` around their launches).
+// A knob is read by its name (include/gsvc_amd_diag.h enum gsvc_knob: the one
+// registry; a bare number does not convert to the enum).
 constexpr int kKnobs = 40;
 #ifdef GSVC_DIAG
 constexpr bool kDiag = true;
-extern int g_knobs[kKnobs];  // gsvc_debug_set(); knob 0 = sum-forward variant, 8 = training tile kernel
+extern int g_knobs[kKnobs];  // gsvc_debug_set()
 extern void *g_debug_ptr;    // gsvc_debug_set_ptr(): diagnostic output buffer
-inline int knob(int k) { return g_knobs[k]; }
+inline int knob(gsvc_knob k) { return g_knobs[k]; }
 inline void *debug_ptr() { return g_debug_ptr; }
 #else
 constexpr bool kDiag = false;
-constexpr int knob(int) { return 0; }
+constexpr int knob(gsvc_knob) { return 0; }
 constexpr void *debug_ptr() { return nullptr; }
 #endif
 // timing.hip: slot, or -1 when not recording; dispatch_ev[2] = the events the
@@ -120,17 +123,6 @@ __device__ __forceinline__ int xcd_runs(int orig, int count) {
 }
 
 // v_cvt_i32_f32 semantics: truncate, saturate, NaN -> 0.
-// 16-byte write-through store (sc1: agent scope): the line leaves the XCD's L2
-// as it is written, so the end-of-kernel release has no dirty line of it to
-// write back; for data the NEXT kernel reads from other XCDs (MI355X_MICROARCH
-// "publish-large").  A vector store; never a scalar-cache one.
-__device__ __forceinline__ void store_wt(float4 *p, float4 v) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 x = {v.x, v.y, v.z, v.w};
-    // s_nop 1: the gfx940+ store-data hazard (raster_sum.hip st_f4)
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
-}
-
 __device__ __forceinline__ int cvt_i32(float f) {
     if (f != f) return 0;
     if (f >= 2147483648.0f) return 2147483647;

@@ -81,7 +81,18 @@ extern "C" int gsvc_abi_version(void) { return GSVC_ABI_VERSION; }
 #ifdef GSVC_DIAG
 // include/gsvc_amd_diag.h: the diagnostic library only
 extern "C" int gsvc_debug_set(int key, int value) {
-    if (key < 0 || key >= gsvc::kKnobs) return -1;
+    switch (key) {  // the live enumerators; a retired or unknown number is refused
+        case GSVC_KNOB_FWD_MODE: case GSVC_KNOB_SPARSE_MAX: case GSVC_KNOB_STAMP:
+        case GSVC_KNOB_TILE_WG256: case GSVC_KNOB_TILE_ABLATE: case GSVC_KNOB_TILE_NO_GROUPS:
+        case GSVC_KNOB_GROUP_MIN: case GSVC_KNOB_NO_SIGMA_CUT: case GSVC_KNOB_RECORD_SLABS:
+        case GSVC_KNOB_BATCH_ID_SLABS: case GSVC_KNOB_KEEP_ORDER: case GSVC_KNOB_ALPHA_BWD_ABLATE:
+        case GSVC_KNOB_SPLAT_ONE_LANE: case GSVC_KNOB_SPARSE_ABLATE: case GSVC_KNOB_GENERIC_RENDER:
+        case GSVC_KNOB_RENDER_STAMPS:
+            break;
+        default:
+            return -1;
+    }
+    static_assert(GSVC_KNOB_RENDER_STAMPS < gsvc::kKnobs, "kKnobs");
     const int old = gsvc::g_knobs[key];
     gsvc::g_knobs[key] = value;
     return old;

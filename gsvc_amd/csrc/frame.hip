@@ -30,67 +30,7 @@
 
 namespace gsvc {
 
-// Append splat i's record to the slab of tiles sub, sub + K, ... of its bbox
-// (row-major), one of the K lanes of the splat; the slot atomics are issued in
-// batches of 8 before their results are waited for.
-template <int K>
-__device__ __forceinline__ int slab_insert(float cx, float cy, int r, int tbx, int tby, int sub,
-                                           float4 r0, float4 r1, float4 r2,
-                                           unsigned *__restrict__ counts,
-                                           float4 *__restrict__ slab, int wt,
-                                           int *__restrict__ ovf) {
-    unsigned x0, y0, x1, y1;
-    tile_bbox(cx, cy, (float)r, tbx, tby, x0, y0, x1, y1);
-    if (x1 <= x0 || y1 <= y0) return 0;
-    const int ntiles = tbx * tby;
-    const unsigned bw = x1 - x0;
-    constexpr int kBatch = 8;
-    unsigned tl[kBatch];
-    int cnt = 0, hits = 0;
-    auto flush = [&]() {
-        unsigned sl[kBatch];
-#pragma unroll
-        for (int k = 0; k < kBatch; ++k)
-            if (k < cnt) sl[k] = atomicAdd(counts + tl[k], 1u);
-#pragma unroll
-        for (int k = 0; k < kBatch; ++k)
-            if (k < cnt && sl[k] >= (unsigned)kTilePix && sl[k] < (unsigned)kCarryCap && ovf) {
-                ovf[(size_t)tl[k] * kOvfSlots + (sl[k] - kTilePix)] = __float_as_int(r2.y);
-            } else if (k < cnt && sl[k] < (unsigned)kTilePix) {
-                float4 *d = slab_rec(slab, ntiles, (int)tl[k], (int)sl[k]);
-                if (kDiag && (wt & 1)) {
-                    store_wt(d, r0);
-                    store_wt(d + 1, r1);
-                    store_wt(d + 2, r2);
-                } else {
-                    d[0] = r0;
-                    d[1] = r1;
-                    d[2] = r2;
-                }
-            }
-        hits += cnt;
-        cnt = 0;
-    };
-    unsigned y = y0 + (unsigned)sub / bw, x = x0 + (unsigned)sub % bw;
-    while (y < y1) {
-        tl[cnt < kBatch ? cnt : 0] = y * (unsigned)tbx + x;
-        if (++cnt == kBatch) flush();
-        x += K;
-        while (x >= x1) {
-            x -= bw;
-            ++y;
-        }
-    }
-    if (cnt) flush();
-    return hits;
-}
-
-// K lanes per splat: each computes the (cheap) projection, lane s writes part
-// of the splat's outputs and inserts every K-th tile of its bbox (K = 1 in
-// production: more lanes did not shorten the insertion, see the launcher).
-
-
-// Diagnostic only (gsvc_debug_set(5, 1) with gsvc_debug_set_ptr): s_memrealtime
+// Diagnostic only (GSVC_KNOB_STAMP = 1 with gsvc_debug_set_ptr): s_memrealtime
 // (100 MHz) stamps per wave -- start, projected, inserted, end -- as int64[4].
 __device__ __forceinline__ long long proj_stamp() {
     long long t;
@@ -98,6 +38,9 @@ __device__ __forceinline__ long long proj_stamp() {
     return t;
 }
 
+// One lane per splat (K = 1, the only instance: 2, 4 and 8 lanes per splat,
+// each inserting every K-th tile of the bbox, did not shorten the insertion --
+// measured at 1080p: equal at 10k splats, 1 lane fastest at 50k).
 template <int K, bool kStamp>
 __global__ __launch_bounds__(kProjThreads) void frame_project_kernel(
     int n, const float *__restrict__ xyz, int xyz_tanh, const float *__restrict__ chol,
@@ -107,7 +50,8 @@ __global__ __launch_bounds__(kProjThreads) void frame_project_kernel(
     unsigned *__restrict__ counts, float4 *__restrict__ slab, int *__restrict__ m_acc,
     int *__restrict__ m_clear, float4 *__restrict__ grad_zero, long long *stamps,
     const int *__restrict__ frame_off, int counts_stride, int m_stride, size_t slab_stride,
-    int wt, int *__restrict__ ids, int *__restrict__ ovf) {
+    int *__restrict__ ids, int *__restrict__ ovf) {
+    static_assert(K == 1, "one lane per splat");
     __shared__ int s_hits[kProjThreads / 64];
     // batched frames (grid.y): this block's frame owns splats [begin, end)
     int begin = 0, end = n;
@@ -125,7 +69,7 @@ __global__ __launch_bounds__(kProjThreads) void frame_project_kernel(
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     long long *st = kStamp ? stamps + 4 * (size_t)(t >> 6) : nullptr;
     if (kStamp && (threadIdx.x & 63) == 0) st[0] = proj_stamp();
-    const int i = begin + t / K, sub = t % K;
+    const int i = begin + t;
     if (blockIdx.x == 0 && threadIdx.x == 0) *m_clear = 0;  // the next frame's slot
     int hits = 0;
     if (i < end) {
@@ -133,14 +77,8 @@ __global__ __launch_bounds__(kProjThreads) void frame_project_kernel(
                                         hh, tbx, tby);
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-        for (int q = sub; q < 4; q += K) {
-            if (q < 3) {
-                const float4 rq = q == 0 ? S.r0 : (q == 1 ? S.r1 : S.r2);
-                if (kDiag && (wt & 1))
-                    store_wt(rec + 3 * i + q, rq);
-                else
-                    rec[3 * i + q] = rq;
-            }
+        for (int q = 0; q < 4; ++q) {
+            if (q < 3) rec[3 * i + q] = q == 0 ? S.r0 : (q == 1 ? S.r1 : S.r2);
             if (q == 3) {
                 xys[i] = S.P.xy;
                 radii[i] = S.P.rad;
@@ -148,15 +86,11 @@ __global__ __launch_bounds__(kProjThreads) void frame_project_kernel(
             if (grad_zero) grad_zero[4 * i + q] = z;
         }
         if (kStamp && (threadIdx.x & 63) == 0) st[1] = proj_stamp();
-        if (S.P.rad > 0) {
-            if (K == 1 && !(kDiag && (wt & 3)))  // paired atomics unless write-through / A/B knob 2 = 4
-                hits = slab_insert_pairs<8>(S.P.xy.x, S.P.xy.y, S.P.rad, tbx, tby, S.r0, S.r1,
-                                            S.r2, counts, slab, wt, ids, kCarryCap,
-                                            ids ? nullptr : ovf);
-            else
-                hits = slab_insert<K>(S.P.xy.x, S.P.xy.y, S.P.rad, tbx, tby, sub, S.r0, S.r1,
-                                      S.r2, counts, slab, wt, ovf);
-        }
+        // paired slot atomics (one 32-bit atomic per tile measured slower:
+        // profiles/r01/paired_atomics/NOTES.md)
+        if (S.P.rad > 0)
+            hits = slab_insert_pairs<8>(S.P.xy.x, S.P.xy.y, S.P.rad, tbx, tby, S.r0, S.r1, S.r2,
+                                        counts, slab, ids, kCarryCap, ids ? nullptr : ovf);
     }
     if (kStamp) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -317,7 +251,7 @@ int frame_project_launch(int n, const float *xyz, int xyz_tanh, const float *cho
     const float hw = 0.5f * (float)img_w, hh = 0.5f * (float)img_h;
     if (ord && frames == 1 && n > 0) {
         const dim3 grid(ceil_div(n, kProjThreads));
-        if constexpr (kDiag) if (knob(5) == 1 && debug_ptr()) {  // diagnostic: per-wave stamps
+        if constexpr (kDiag) if (knob(GSVC_KNOB_STAMP) == 1 && debug_ptr()) {  // diagnostic: per-wave stamps
             hipLaunchKernelGGL(frame_project_ordered_kernel<true>, grid, dim3(kProjThreads), 0, s, n,
                                ord->order, xyz, xyz_tanh, chol, chol_bound, feat, rgb_w, opac, hw,
                                hh, tbx, tby, w.xys, w.radii, w.rec,
@@ -338,18 +272,11 @@ int frame_project_launch(int n, const float *xyz, int xyz_tanh, const float *cho
         timing_end(s, tslot, kTimingProject);
         return check_launch("frame projection (ordered)");
     }
-    // lanes per splat: 1 unless gsvc_debug_set(4, k) picks 2, 4 or 8 (A/B knob;
-    // measured at 1080p: equal at 10k splats, 1 lane fastest at 50k)
-    // id_slab (A/B knob 24): 4-byte ids instead of the 48-byte records, paired atomics
-    const int k = !id_slab && (knob(4) == 2 || knob(4) == 4 || knob(4) == 8) ? knob(4) : 1;
+    // id_slab: 4-byte ids instead of the 48-byte records
     const size_t slab_stride = slab_frame_f4(tbx * tby);
-    // plain record stores; A/B knob 6 = 1 writes them through (sc1): measured
-    // slower (projection 7.1 -> 9.8 us at 10k: each scattered 16-byte sc1 store
-    // is its own fabric write) and no faster for the composite's loads
-    // bit 0: write-through record stores (A/B knob 6 = 1); bit 1: one 32-bit
-    // slot atomic per tile instead of the pairs (A/B knob 2 = 4).  Measured
-    // with the isolation runs of profiles/r01/paired_atomics/NOTES.md.
-    const int wt = id_slab ? 0 : (knob(6) == 1 ? 1 : 0) | (knob(2) == 4 ? 2 : 0);
+    // plain record stores: written through (sc1) they measured slower
+    // (projection 7.1 -> 9.8 us at 10k: each scattered 16-byte sc1 store is its
+    // own fabric write) and no faster for the composite's loads
     if (frames > 1 && !frame_off) return set_error(GSVC_ERR_ARG, "frame projection: frame offsets");
     const int per = frames > 1 ? max_frame_n : n;
     if (frames > 1 && per <= 0) {
@@ -359,41 +286,25 @@ int frame_project_launch(int n, const float *xyz, int xyz_tanh, const float *cho
         return check_launch("frame projection");
     }
     if (per > 0) {
-        // workgroup size: 256 unless A/B knob 1 picks 64 or 128
-        const int bs = knob(1) == 64 || knob(1) == 128 ? knob(1) : kProjThreads;
-        const dim3 grid(ceil_div(per, bs / k), frames > 1 ? frames : 1);
-#define GSVC_FRAME_PROJECT(K)                                                                    \
-    {                                                                                            \
-        hipEvent_t tev[2];                                                                       \
-        const int tslot = timing_begin(s, tev, kTimingProject);                                  \
-        launch_timed(frame_project_kernel<K, false>, grid, dim3(bs), 0, s, tev, n, xyz,          \
-                     xyz_tanh, chol, chol_bound, feat, rgb_w, opac, hw, hh, tbx, tby, w.xys,     \
-                     w.radii, w.rec, f.counts, w.slab, f.m_acc, f.m_clear, grad_zero,            \
-                     (long long *)nullptr, frames > 1 ? frame_off : (const int *)nullptr,        \
-                     f.counts_stride, f.m_stride, slab_stride, wt, id_slab, w.ovf);              \
-        timing_end(s, tslot, kTimingProject);                                                    \
-    }
-        if constexpr (kDiag) if (knob(5) == 1 && debug_ptr()) {  // diagnostic: per-wave stamps
+        const dim3 grid(ceil_div(per, kProjThreads), frames > 1 ? frames : 1);
+        if constexpr (kDiag) if (knob(GSVC_KNOB_STAMP) == 1 && debug_ptr()) {  // diagnostic: per-wave stamps
             auto kfn = frame_project_kernel<1, true>;
-            hipLaunchKernelGGL(kfn, grid, dim3(bs), 0, s, n, xyz, xyz_tanh, chol,
+            hipLaunchKernelGGL(kfn, grid, dim3(kProjThreads), 0, s, n, xyz, xyz_tanh, chol,
                                chol_bound, feat, rgb_w, opac, hw, hh, tbx, tby, w.xys, w.radii,
                                w.rec, f.counts, w.slab, f.m_acc, f.m_clear, grad_zero,
                                reinterpret_cast<long long *>(debug_ptr()),
                                frames > 1 ? frame_off : nullptr, f.counts_stride, f.m_stride,
-                               slab_stride, wt, id_slab, w.ovf);
+                               slab_stride, id_slab, w.ovf);
             return check_launch("frame projection");
         }
-        if constexpr (kDiag) {
-            switch (k) {
-                case 2: GSVC_FRAME_PROJECT(2); break;
-                case 8: GSVC_FRAME_PROJECT(8); break;
-                case 4: GSVC_FRAME_PROJECT(4); break;
-                default: GSVC_FRAME_PROJECT(1); break;
-            }
-        } else {
-            GSVC_FRAME_PROJECT(1);
-        }
-#undef GSVC_FRAME_PROJECT
+        hipEvent_t tev[2];
+        const int tslot = timing_begin(s, tev, kTimingProject);
+        launch_timed(frame_project_kernel<1, false>, grid, dim3(kProjThreads), 0, s, tev, n, xyz,
+                     xyz_tanh, chol, chol_bound, feat, rgb_w, opac, hw, hh, tbx, tby, w.xys,
+                     w.radii, w.rec, f.counts, w.slab, f.m_acc, f.m_clear, grad_zero,
+                     (long long *)nullptr, frames > 1 ? frame_off : (const int *)nullptr,
+                     f.counts_stride, f.m_stride, slab_stride, id_slab, w.ovf);
+        timing_end(s, tslot, kTimingProject);
     } else if (dev_zero(f.m_acc, sizeof(int), s) != GSVC_OK)
         return set_error(GSVC_ERR_HIP, "frame projection: memset failed");
     return check_launch("frame projection");
@@ -448,10 +359,10 @@ static int render_frames(int frames, const int *frame_off_host, const int *frame
     // the records by id from w.rec (the slab memory holds T x kCarryCap ids: a
     // tile of up to 1024 entries sorts its first 256 from them).
     // Batched frames and dense frames (the banded kernel) keep the records;
-    // A/B knob 24 = 1 (diagnostic library) too.
+    // GSVC_KNOB_RECORD_SLABS = 1 (diagnostic library) too.
     int *id_slab = nullptr;
-    if (!sum_forward_dense(density_hint, ntiles, frames) && knob(24) != 1 &&
-        (frames == 1 || knob(25) == 1))  // A/B knob 25 = 1: batched frames too
+    if (!sum_forward_dense(density_hint, ntiles, frames) && knob(GSVC_KNOB_RECORD_SLABS) != 1 &&
+        (frames == 1 || knob(GSVC_KNOB_BATCH_ID_SLABS) == 1))  // A/B: batched frames too
         id_slab = reinterpret_cast<int *>(w.slab);
     // A sparse single frame (<= kPlainProjMaxPerTile entries per tile by the
     // hint) projects in id order with plain paired atomics: the windowed
@@ -459,9 +370,9 @@ static int render_frames(int frames, const int *frame_off_host, const int *frame
     // 7.9-8.4 us).  A refresh call still takes the ordered kernel, which writes
     // the strip keys its sort reads -- a refresh whose projection skipped them
     // sorted uninitialised keys and ids into the order, and the next ordered
-    // call gathered splats through it (the round-4 fault).  Knob 27
-    // = 1 keeps the order at any density (A/B).
-    const bool plain = use_order && !refresh && knob(27) != 1 &&
+    // call gathered splats through it (the round-4 fault).
+    // GSVC_KNOB_KEEP_ORDER = 1 keeps the order at any density (A/B).
+    const bool plain = use_order && !refresh && knob(GSVC_KNOB_KEEP_ORDER) != 1 &&
                        (long long)density_hint <= (long long)kPlainProjMaxPerTile * ntiles;
     int rc = frame_project_launch(num_points, xyz, xyz_tanh, cholesky, cholesky_bound, features,
                                   rgb_w, opacity, img_height, img_width, w, f, nullptr, s, frames,

@@ -26,7 +26,7 @@ template <int kB>
 __device__ __forceinline__ int slab_insert_pairs(float cx, float cy, int r, int tbx, int tby,
                                                  float4 r0, float4 r1, float4 r2,
                                                  unsigned *__restrict__ counts,
-                                                 float4 *__restrict__ slab, int wt,
+                                                 float4 *__restrict__ slab,
                                                  int *__restrict__ ids = nullptr,
                                                  int ids_cap = kTilePix,
                                                  int *__restrict__ ovf = nullptr) {
@@ -247,7 +247,7 @@ __device__ __forceinline__ int slab_insert_window(const SplatOut &S, unsigned x0
     int hits = 0;
     if (vis && !(agg && small))
         hits = slab_insert_pairs<8>(S.P.xy.x, S.P.xy.y, S.P.rad, tbx, tby, S.r0, S.r1, S.r2,
-                                    counts, slab, 0, ids, ids_cap, ovf);
+                                    counts, slab, ids, ids_cap, ovf);
     if (agg) {
         const int cells = ww * wh;
         for (int c = tid; c < cells; c += kThr) s_cnt[c] = 0u;

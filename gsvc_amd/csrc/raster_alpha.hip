@@ -66,8 +66,7 @@ __global__ __launch_bounds__(64) void raster_alpha_fwd_kernel(
     int tbx, int img_w, int img_h, int ntiles, const int *__restrict__ ids,
     const int2 *__restrict__ bins, const float2 *__restrict__ xys, const float *__restrict__ conics,
     const float *__restrict__ colors, const float *__restrict__ opac, const float *__restrict__ bg,
-    float *__restrict__ out, float *__restrict__ final_Ts, int *__restrict__ final_idx,
-    int group_min) {
+    float *__restrict__ out, float *__restrict__ final_Ts, int *__restrict__ final_idx) {
     // staged entries (slot kAChunk: the lists' no-op sentinel, sigma = +inf),
     // their 4x4 blocks and the 16 groups' lists [iteration][group]
     __shared__ float4 s_geo[kAChunk + 1];  // x, y, 0.5a, b
@@ -101,7 +100,7 @@ __global__ __launch_bounds__(64) void raster_alpha_fwd_kernel(
     for (int base = 0; base < n; base += kAChunk) {
         if (__all(done[0] && done[1] && done[2] && done[3])) break;
         const int cnt = min(kAChunk, n - base);
-        const bool grouped = cnt > group_min;
+        const bool grouped = cnt > kAGroupMin;
         if (lane < cnt) {
             const int g = ids[range.x + base + lane];
             const float2 xy = xys[g];
@@ -187,10 +186,9 @@ __device__ __forceinline__ float rows_to_last(float v) {
 // broadcasts) into lane 63, which keeps the entry's 9 sums in LDS; once per
 // 64-entry chunk they go to the splat's record, one 64-byte atomic request per
 // (splat, tile).  An entry no pixel of the tile takes costs no sums.
-// Round 4's kernel (256 threads = 256 pixels, per entry and wave 9 DPP row
-// sums and LDS float atomics: 111 us at 1080p / 50k) stays in the diagnostic
-// library as raster_alpha_bwd_kernel_r4 (A/B knob 9 = 1).
-// kAbl (diagnostic library, A/B knob 30, wrong results): bit 0 no per-entry
+// (Round 4's kernel -- 256 threads = 256 pixels, per entry and wave 9 DPP row
+// sums and LDS float atomics -- took 111 us at 1080p / 50k and is gone.)
+// kAbl (diagnostic library, GSVC_KNOB_ALPHA_BWD_ABLATE, wrong results): bit 0 no per-entry
 // sums, bit 1 no pixel work
 template <int kAbl = 0>
 __global__ __launch_bounds__(64, 5) void raster_alpha_bwd_kernel(
@@ -368,137 +366,6 @@ __global__ __launch_bounds__(64, 5) void raster_alpha_bwd_kernel(
     }
 }
 
-#ifdef GSVC_DIAG
-// Round 4's backward (diagnostic library, A/B knob 9 = 1): pixel-parallel, 256
-// threads = 256 pixels; per entry each wave sums its 9 partial gradients per
-// 16-lane row with DPP adds, the rows' last lanes add them to an LDS record
-// with LDS float atomics, and once per 256-entry chunk the tile's records go
-// to HBM as one 64-byte atomic request per (splat, tile).
-__global__ __launch_bounds__(256) void raster_alpha_bwd_kernel_r4(
-    int tbx, int img_w, int img_h, int ntiles, const int *__restrict__ ids,
-    const int2 *__restrict__ bins, const float2 *__restrict__ xys, const float *__restrict__ conics,
-    const float *__restrict__ colors, const float *__restrict__ opac, const float *__restrict__ bg,
-    const float *__restrict__ final_Ts, const int *__restrict__ final_idx,
-    const float *__restrict__ v_out, const float *__restrict__ v_out_alpha,
-    float *__restrict__ grad) {
-    __shared__ float4 s_geo[kTilePix];  // x, y, a, b
-    __shared__ float4 s_col[kTilePix];  // c, opacity, r, g
-    __shared__ float s_blu[kTilePix];
-    __shared__ int s_gid[kTilePix];
-    __shared__ float s_acc[kTilePix][9];
-    __shared__ int s_max[4];
-    const int tile = xcd_remap(blockIdx.x, ntiles);
-    const int ty = tile / tbx, tx = tile - ty * tbx;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int pi = ty * kTile + (tid >> 4), pj = tx * kTile + (tid & 15);
-    const bool inside = pi < img_h && pj < img_w;
-    const float px = (float)pj, py = (float)pi;
-    // backward.cu:160: out-of-image threads clamp to the last pixel; they are
-    // never valid, so only their loads matter.
-    const size_t p = inside ? (size_t)pi * (size_t)img_w + (size_t)pj : 0;
-    const float T_final = inside ? final_Ts[p] : 1.0f;
-    float T = T_final;
-    float buf0 = 0.f, buf1 = 0.f, buf2 = 0.f;
-    const int bin_final = inside ? final_idx[p] : (-2147483647 - 1);
-    const float vo0 = inside ? v_out[3 * p] : 0.f, vo1 = inside ? v_out[3 * p + 1] : 0.f;
-    const float vo2 = inside ? v_out[3 * p + 2] : 0.f;
-    const float voa = inside ? v_out_alpha[p] : 0.f;
-    const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
-    int f = bin_final;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) f = max(f, __shfl_xor(f, off, 64));
-    if (lane == 0) s_max[tid >> 6] = f;
-    __syncthreads();
-    const int maxf = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
-    const int2 range = bins[tile];
-    const int kend = min(range.y, maxf == (-2147483647 - 1) ? maxf : maxf + 1);
-
-    // chunks of <= 256 entries, back to front
-    for (int ce = kend; ce > range.x; ce -= kTilePix) {
-        const int cs = max(range.x, ce - kTilePix);
-        const int n = ce - cs;
-        if (tid < n) {
-            const int g = ids[cs + tid];
-            s_gid[tid] = g;
-            const float2 xy = xys[g];
-            s_geo[tid] = make_float4(xy.x, xy.y, conics[3 * g], conics[3 * g + 1]);
-            s_col[tid] = make_float4(conics[3 * g + 2], opac[g], colors[3 * g], colors[3 * g + 1]);
-            s_blu[tid] = colors[3 * g + 2];
-#pragma unroll
-            for (int c = 0; c < 9; ++c) s_acc[tid][c] = 0.f;
-        }
-        __syncthreads();
-        for (int t = n - 1; t >= 0; --t) {
-            const int k = cs + t;
-            bool valid = inside && k <= bin_final;
-            float4 G, C;
-            float dx = 0.f, dy = 0.f, vis = 0.f, al = 0.f;
-            if (valid) {
-                G = s_geo[t];
-                C = s_col[t];
-                dx = G.x - px;
-                dy = G.y - py;
-                const float s = splat_sigma_h(0.5f * G.z, G.w, 0.5f * C.x, dx, dy);
-                vis = exp_neg(s);
-                al = fminf(0.99f, C.y * vis);
-                if (s < 0.0f || al < kAlphaMin) valid = false;
-            }
-            if (!__any(valid)) continue;
-            float g_r = 0.f, g_g = 0.f, g_b = 0.f, g_c0 = 0.f, g_c1 = 0.f, g_c2 = 0.f;
-            float g_x = 0.f, g_y = 0.f, g_o = 0.f;
-            if (valid) {
-                const float ra = 1.0f / (1.0f - al);
-                T = T * ra;
-                const float fac = al * T;
-                const float r = C.z, gg = C.w, bb = s_blu[t];
-                const float tfra = T_final * ra;
-                float v_alpha = (r * T - buf0 * ra) * vo0;
-                v_alpha = fmaf(gg * T - buf1 * ra, vo1, v_alpha);
-                v_alpha = fmaf(bb * T - buf2 * ra, vo2, v_alpha);
-                v_alpha = fmaf(tfra, voa, v_alpha);
-                v_alpha = fmaf(-tfra * bg0, vo0, v_alpha);
-                v_alpha = fmaf(-tfra * bg1, vo1, v_alpha);
-                v_alpha = fmaf(-tfra * bg2, vo2, v_alpha);
-                buf0 = fmaf(r, fac, buf0);
-                buf1 = fmaf(gg, fac, buf1);
-                buf2 = fmaf(bb, fac, buf2);
-                const float v_sigma = (-C.y * vis) * v_alpha;
-                g_r = fac * vo0;
-                g_g = fac * vo1;
-                g_b = fac * vo2;
-                const float hs = 0.5f * v_sigma;
-                g_c0 = (hs * dx) * dx;
-                g_c1 = (hs * dx) * dy;
-                g_c2 = (hs * dy) * dy;
-                g_x = v_sigma * fmaf(G.z, dx, G.w * dy);
-                g_y = v_sigma * fmaf(G.w, dx, C.x * dy);
-                g_o = vis * v_alpha;
-            }
-            // the entry's sums over the wave: per 16-lane row by DPP, then the
-            // last lane of each row adds its row's sums into the entry's LDS
-            // accumulator (the row order of these adds is not fixed: float
-            // atomics, as the reference's warp sums + atomicAdd)
-            {
-                const float gs[9] = {row_sum16(g_x), row_sum16(g_y), row_sum16(g_c0),
-                                     row_sum16(g_c1), row_sum16(g_c2), row_sum16(g_r),
-                                     row_sum16(g_g), row_sum16(g_b), row_sum16(g_o)};
-                if ((lane & 15) == 15) {
-#pragma unroll
-                    for (int c = 0; c < 9; ++c) atomicAdd(&s_acc[t][c], gs[c]);
-                }
-            }
-        }
-        __syncthreads();
-        for (int q = tid; q < n * 16; q += kTilePix) {
-            const int e2 = q >> 4, c = q & 15;
-            if (c < 9) unsafeAtomicAdd(grad + (size_t)s_gid[e2] * 16 + c, s_acc[e2][c]);
-        }
-        __syncthreads();
-    }
-}
-
-#endif
-
 }  // namespace gsvc
 
 using namespace gsvc;
@@ -523,9 +390,7 @@ extern "C" int gsvc_rasterize_forward(int tbx, int tby, int tbz, int block_x, in
     launch_timed(raster_alpha_fwd_kernel, dim3(ntiles), dim3(64), 0, s, tev, tbx, (int)img_width,
                  (int)img_height, ntiles, gaussian_ids_sorted, (const int2 *)tile_bins,
                  (const float2 *)xys, conics, colors, opacities, background, out_img, final_Ts,
-                 final_idx,
-                 // A/B knob 18 = v > 0: list threshold v - 1
-                 knob(18) > 0 ? knob(18) - 1 : kAGroupMin);
+                 final_idx);
     timing_end(s, tslot, kTimingAlphaFwd);
     return check_launch("rasterize_forward");
 }
@@ -550,20 +415,10 @@ extern "C" int gsvc_rasterize_backward(unsigned img_height, unsigned img_width, 
     if (ntiles == 0 || num_points == 0) return GSVC_OK;
     hipEvent_t tev[2];
     const int tslot = timing_begin(s, tev, kTimingAlphaBwd);
-#ifdef GSVC_DIAG
-    if (knob(9) == 1) {  // A/B: round 4's 256-thread kernel
-        launch_timed(raster_alpha_bwd_kernel_r4, dim3(ntiles), dim3(256), 0, s, tev, tbx,
-                     (int)img_width, (int)img_height, ntiles, gaussian_ids_sorted,
-                     (const int2 *)tile_bins, (const float2 *)xys, conics, colors, opacities,
-                     background, final_Ts, final_idx, v_output, v_output_alpha, grad_records);
-        timing_end(s, tslot, kTimingAlphaBwd);
-        return check_launch("rasterize_backward");
-    }
-#endif
     auto bwd = raster_alpha_bwd_kernel<0>;
     if constexpr (kDiag) {
-        if (knob(30) == 1) bwd = raster_alpha_bwd_kernel<1>;
-        if (knob(30) == 2) bwd = raster_alpha_bwd_kernel<2>;
+        if (knob(GSVC_KNOB_ALPHA_BWD_ABLATE) == 1) bwd = raster_alpha_bwd_kernel<1>;
+        if (knob(GSVC_KNOB_ALPHA_BWD_ABLATE) == 2) bwd = raster_alpha_bwd_kernel<2>;
     }
     launch_timed(bwd, dim3(ntiles), dim3(64), 0, s, tev, tbx, (int)img_width,
                  (int)img_height, ntiles, gaussian_ids_sorted, (const int2 *)tile_bins,

@@ -20,12 +20,15 @@ struct SumFwdArgs {
     int tbx, img_w, img_h, ntiles, sparse_max, layout;
     bool vec;      // HWC: W % 4 == 0 and 16-byte aligned outputs
     bool vec_chw;  // CHW: W % 4 == 0, H*W % 4 == 0, 16-byte aligned
-    int store_policy;  // CHW plane stores: kStore* (gsvc_debug_set(7) selects)
-    int spec_slots;    // frame path: slab records loaded with the count (<= kHeadSlots)
+    // unused0 / unused1: the words of two retired A/B arguments, and spec_slots
+    // still an argument (always kHeadSlots): the composite kernels' code follows
+    // the argument layout, and they are not to move (64 VGPRs, 8 waves per SIMD).
+    int unused0;
+    int spec_slots;    // frame path: slab records loaded with the count (kHeadSlots)
     int group_min;     // sparse chunks of <= this many entries skip the lane-group lists
-    int cut;           // sparse render chunks may take the sigma-threshold blend (knob 19 = 1: never)
-    int xcd_off;       // diagnostic A/B (knob 37): 1 tiles in dispatch order, 4 xcd_remap ranges
-    int ablate;        // diagnostic (knob 36, wrong results): sparse tile phases skipped --
+    int cut;           // sparse render chunks may take the sigma-threshold blend (GSVC_KNOB_NO_SIGMA_CUT: never)
+    int unused1;
+    int ablate;        // diagnostic (GSVC_KNOB_SPARSE_ABLATE, wrong results): sparse tile phases skipped --
                        // 1 blend, 2 stores, 4 record loads, 8 ranking,
                        // 16 every load (raster_render_ids_kernel)
     int ids_cap;       // id slabs: slots per tile (kTilePix, or kCarryCap for wide slabs)
@@ -80,7 +83,7 @@ struct SumFwdArgs {
 
 // sum_fwd_args_init zeroes every field (rec, stamps, m_dev NULL; HWC layout);
 // callers set the rest.  sum_forward_launch launches the kernel variant for
-// ``density_hint`` (or the gsvc_debug_set(0) override).
+// ``density_hint`` (or the GSVC_KNOB_FWD_MODE override).
 void sum_fwd_args_init(SumFwdArgs &A);
 int sum_forward_launch(SumFwdArgs &A, int density_hint, hipStream_t s);
 // The launcher's sparse / banded choice from the caller's intersection count

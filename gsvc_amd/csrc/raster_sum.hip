@@ -51,7 +51,7 @@
 namespace gsvc {
 
 constexpr int kChunk = 64;
-// Frame path: the first spec_slots (<= kHeadSlots) slab records are loaded in
+// Frame path: the first spec_slots (= kHeadSlots) slab records are loaded in
 // the count's round trip (speculatively: most tiles have that few); slot j of a
 // tile is in its head (j < kHeadSlots) or at index j of its body.
 __device__ __forceinline__ const float4 *slot_rec(const float4 *head, const float4 *body, int j) {
@@ -62,33 +62,32 @@ constexpr int kSlice = 220;  // float4s of LDS per wave (3.4 KB; sum_fwd_sparse'
 // Forward kernel modes.  Production: the launcher picks kModeSparse (one wave
 // per tile) when the frame averages <= 8 entries per tile and kModeBanded
 // (two waves per tile) above, from the intersection count the caller already
-// holds (gsvc_rasterize_sum_forward_auto).  gsvc_debug_set(0, mode) forces a
+// holds (gsvc_rasterize_sum_forward_auto).  GSVC_KNOB_FWD_MODE forces a
 // mode for tools/kbench.py:
 //   1 sparse path only     2 banded path only
 //   3 per-tile choice (2 waves per tile) with timestamps (diagnostic)
 //   4 banded, no blending  5 banded, no stores   (ablations)
-//   6 per-tile choice (2 waves per tile; threshold gsvc_debug_set(3, t))
+//   6 per-tile choice (2 waves per tile; threshold GSVC_KNOB_SPARSE_MAX)
 //   7 sparse path with 4 timestamps per tile (start, staged, blended, stores
 //     drained) into the buffer of gsvc_debug_set_ptr (diagnostic)
 // A per-tile choice inside one launch was measured slower than either pure
 // mode: a 128-thread workgroup whose second wave exits at once still halves
 // the dispatch rate of sparse tiles.
 enum { kModeAdaptive = 6, kModeSparse = 1, kModeBanded = 2, kModeStamp = 3, kModeNoBlend = 4,
-       kModeNoStore = 5, kModeSparseStamp = 7, kModeSparsePrio = 8, kModeSparseIds = 9 };
+       kModeNoStore = 5, kModeSparseStamp = 7, kModeSparseIds = 9 };
 // kModeSparseIds: kModeSparse over 4-byte id slabs (A.id_counts / A.ids_rw, the
 // entries' records gathered by id from A.rec): the single-frame render -- its
 // projection appends ids instead of 48-byte records (trained 1080p / 50k:
 // projection 14.9 -> 10.5 us, composite 20.7 -> 21.4, frame 25.8k -> 28.8k fps;
-// 10k equal; profiles/r04/id_slabs/).  A/B knob 24 = 1 restores the records.
-// kModeSparsePrio: kModeSparse with the wave priority raised over the staging
-// (s_setprio 3 until the blend; A/B knob 17 = 1 selects it for the sparse launches)
+// 10k equal; profiles/r04/id_slabs/).  GSVC_KNOB_RECORD_SLABS = 1 restores the
+// records.
 // Banded (two waves per tile) only past this many entries per tile on average.
 // Measured with the lane-group lists (1080p, tools/fbench.py, profiles/r02/composite_modes/):
 // sparse wins from 3 to 62 entries per tile (trained 50k, 28 per tile: 43.0 vs 48.0 us per
 // frame; 62 per tile: 82.1 vs 93.8) and ties at 107 (138.4 vs 137.2).
 constexpr int kDenseEntriesPerTile = 96;
 // A sparse tile's chunk of at most this many entries is blended by every lane
-// without the lane-group lists (A/B knob 15 = v > 0 sets it to v - 1).
+// without the lane-group lists (GSVC_KNOB_GROUP_MIN = v > 0 sets it to v - 1).
 constexpr int kGroupMinDefault = 24;
 
 // Diagnostic only (kModeStamp): s_memrealtime (100 MHz) stamps per tile,
@@ -102,7 +101,7 @@ __device__ __forceinline__ long long stamp() {
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 // Diagnostic library only: the id-slab render's phases stamped per tile when
-// A.stamps is set (knob 39 = 1 with gsvc_debug_set_ptr; int64[ntiles][8]: start,
+// A.stamps is set (GSVC_KNOB_RENDER_STAMPS = 1 with gsvc_debug_set_ptr; int64[ntiles][8]: start,
 // ids arrived, staged, blended, stores drained, entry count)
 template <int kMode>
 constexpr bool kIdStampMode = kDiag && kMode == kModeSparseIds;
@@ -201,10 +200,10 @@ __device__ __forceinline__ bool ellipse_hits_rect(float x, float y, float a, flo
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-// Plane stores of the render layout, by cache policy: streaming write-through
-// (nt sc1, production: the lines leave L2 as they are written, so the
-// end-of-kernel release has ~25 MB less to write back -- composite 10.6 ->
-// 9.5 us at 1080p), plain (write-back L2), sc1, sc0 sc1, or nt alone.
+// Plane stores of the render layout: streaming write-through (nt sc1: the
+// lines leave L2 as they are written, so the end-of-kernel release has ~25 MB
+// less to write back -- composite 10.6 -> 9.5 us at 1080p; plain write-back,
+// sc1, sc0 sc1 and nt alone were the other policies measured).
 //
 // Every inline-asm store of more than 64 bits ends with ``s_nop 1``: the store
 // reads its data VGPRs after it issues, and on gfx940+ a VALU write to one of
@@ -215,38 +214,14 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // one 16-lane pass of the wave stored the new value now and then (DESIGN.md
 // §12, tools/store_hazard_scan.py, tests/test_store_hazard.py).  The trailing
 // nop makes the asm safe wherever the compiler places it.
-enum { kStoreNtSc1 = 0, kStorePlain = 1, kStoreSc1 = 2, kStoreSc01 = 3, kStoreNt = 4 };
-
-__device__ __forceinline__ void st_f4(float *p, float a, float b, float c, float d, int policy) {
+__device__ __forceinline__ void st_f4(float *p, float a, float b, float c, float d) {
     const v4f v = {a, b, c, d};
-    if (!kDiag) policy = kStoreNtSc1;  // the product's one policy
-    switch (policy) {
-    case kStoreNt: __builtin_nontemporal_store(v, reinterpret_cast<v4f *>(p)); break;
-    case kStoreSc1: asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory"); break;
-    case kStoreSc01:
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-        break;
-    case kStoreNtSc1:
-        asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-        break;
-    default: *reinterpret_cast<v4f *>(p) = v; break;
-    }
+    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
-__device__ __forceinline__ void st_f2(float *p, float a, float b, int policy) {
+__device__ __forceinline__ void st_f2(float *p, float a, float b) {
     const v2f v = {a, b};
-    if (!kDiag) policy = kStoreNtSc1;  // the product's one policy
-    switch (policy) {
-    case kStoreNt: __builtin_nontemporal_store(v, reinterpret_cast<v2f *>(p)); break;
-    case kStoreSc1: asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); break;
-    case kStoreSc01:
-        asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-        break;
-    case kStoreNtSc1:
-        asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
-        break;
-    default: *reinterpret_cast<v2f *>(p) = v; break;
-    }
+    asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
 }
 
 __device__ __forceinline__ float clamp01(float x) {
@@ -440,7 +415,6 @@ __device__ __forceinline__ void sum_fwd_sparse(const SumFwdArgs &A, int tile, in
             }
         };
         if (cnt <= kGroupMin) {
-            if (kMode == kModeSparsePrio) __builtin_amdgcn_s_setprio(0);
             // a few entries: every lane walks them all (the lists would cost
             // more than the pairs they skip)
             if (base == 0) phase_stamp<kMode>(A, tile, 1, 2);
@@ -467,7 +441,6 @@ __device__ __forceinline__ void sum_fwd_sparse(const SumFwdArgs &A, int tile, in
             maxlen = max(maxlen, __popcll(mg));
         }
         wave_lds_sync();
-        if (kMode == kModeSparsePrio) __builtin_amdgcn_s_setprio(0);
         if (base == 0) phase_stamp<kMode>(A, tile, 1, 2);
         // the lane's 4x4 block of the tile
         const unsigned char *ml = s_list + (((lane >> 4) << 2) | (lane & 3));
@@ -504,11 +477,9 @@ __device__ __forceinline__ void sum_fwd_sparse(const SumFwdArgs &A, int tile, in
         if (pi < A.img_h && !(kDiag && (A.ablate & 2))) {
             const size_t hw = (size_t)A.img_w * (size_t)A.img_h;
             float *o = A.out + (size_t)pi * (size_t)A.img_w + (size_t)pj;
-            st_f4(o, plane_val(A, r0), plane_val(A, r1), plane_val(A, r2), plane_val(A, r3), A.store_policy);
-            st_f4(o + hw, plane_val(A, g0), plane_val(A, g1), plane_val(A, g2), plane_val(A, g3),
-                  A.store_policy);
-            st_f4(o + 2 * hw, plane_val(A, b0), plane_val(A, b1), plane_val(A, b2), plane_val(A, b3),
-                  A.store_policy);
+            st_f4(o, plane_val(A, r0), plane_val(A, r1), plane_val(A, r2), plane_val(A, r3));
+            st_f4(o + hw, plane_val(A, g0), plane_val(A, g1), plane_val(A, g2), plane_val(A, g3));
+            st_f4(o + 2 * hw, plane_val(A, b0), plane_val(A, b1), plane_val(A, b2), plane_val(A, b3));
             if (A.final_idx)
                 *reinterpret_cast<int4 *>(A.final_idx + (o - A.out)) = make_int4(l0, l1, l2, l3);
         }
@@ -538,7 +509,7 @@ __device__ __forceinline__ void sum_fwd_sparse(const SumFwdArgs &A, int tile, in
             if (ty * kTile + row < A.img_h) {
                 float *o = A.out + tile_base + (size_t)row * A.img_w * 3 + cc * 4;
                 const float4 q = s_slice[c];
-                st_f4(o, q.x, q.y, q.z, q.w, A.store_policy);
+                st_f4(o, q.x, q.y, q.z, q.w);
             }
         }
         if (pi < A.img_h && A.final_idx) {
@@ -685,9 +656,9 @@ __device__ __forceinline__ void sum_fwd_band(const SumFwdArgs &A, int tile, int 
         if (pi < A.img_h) {
             const size_t hw = (size_t)A.img_w * (size_t)A.img_h;
             float *o = A.out + (size_t)pi * (size_t)A.img_w + (size_t)pj;
-            st_f2(o, plane_val(A, ar.x), plane_val(A, ar.y), A.store_policy);
-            st_f2(o + hw, plane_val(A, ag.x), plane_val(A, ag.y), A.store_policy);
-            st_f2(o + 2 * hw, plane_val(A, ab.x), plane_val(A, ab.y), A.store_policy);
+            st_f2(o, plane_val(A, ar.x), plane_val(A, ar.y));
+            st_f2(o + hw, plane_val(A, ag.x), plane_val(A, ag.y));
+            st_f2(o + 2 * hw, plane_val(A, ab.x), plane_val(A, ab.y));
             if (A.final_idx) *reinterpret_cast<int2 *>(A.final_idx + (o - A.out)) = make_int2(l0, l1);
         }
         return;
@@ -708,8 +679,7 @@ __device__ __forceinline__ void sum_fwd_band(const SumFwdArgs &A, int tile, int 
                 const int row = c / 12, cc = c - row * 12;
                 if (row0 + row < A.img_h) {
                     const float4 q = s_slice[c];
-                    st_f4(A.out + base_off + (size_t)row * A.img_w * 3 + cc * 4, q.x, q.y, q.z, q.w,
-                          A.store_policy);
+                    st_f4(A.out + base_off + (size_t)row * A.img_w * 3 + cc * 4, q.x, q.y, q.z, q.w);
                 }
             }
         }
@@ -749,29 +719,22 @@ __device__ __forceinline__ void write_sorted_ids(const SumFwdArgs &A, int tile, 
 // (2 and 4 one-tile waves per workgroup were measured, round 5: within +-2 %,
 // not kept)
 template <int kMode, bool kIdx>
-__global__ __launch_bounds__(kMode == kModeSparse || kMode == kModeSparseStamp || kMode == kModeSparsePrio ||
+__global__ __launch_bounds__(kMode == kModeSparse || kMode == kModeSparseStamp ||
                               kMode == kModeSparseIds ? 64 : 128, 8) void
 raster_sum_fwd_kernel(SumFwdArgs A) {
-    constexpr bool kOneWave = kMode == kModeSparse || kMode == kModeSparseStamp || kMode == kModeSparsePrio ||
+    constexpr bool kOneWave = kMode == kModeSparse || kMode == kModeSparseStamp ||
                               kMode == kModeSparseIds;
     // id slabs: the op path's autograd forward (kIdx, or sparse / banded
     // without final_idx) and the single-frame render
     constexpr bool kIds = kIdx || kMode == kModeSparseIds || kMode == kModeBanded;
     __shared__ float4 s_buf[kOneWave ? 1 : 2][kSlice];
     __shared__ int s_ids[1][kTilePix];  // the tile's sorted ids
-    // raised wave priority over the staging (loads, ranking, lists): the
-    // arbiter favours older waves, so a young wave would otherwise wait behind
-    // its elders' blending to issue its round trips (train.hip, same reason)
-    if (kMode == kModeSparsePrio) __builtin_amdgcn_s_setprio(3);
     const int w = kOneWave ? 0 : (threadIdx.x >> 6);
     constexpr int sub = 0;
     // runs of 16 tiles dealt over the XCDs, as the training tile kernel
     // (fbench: 10k frame 17.0 vs 17.3-17.4 us, the textured video's dense
-    // frame 116 at M = 894k 251.5-252.6 vs 263.9-264.6, trained 50k equal;
-    // A/B knob 37: 1 dispatch order, 4 contiguous XCD ranges)
-    int tile = !(kDiag && A.xcd_off) ? xcd_runs<16>(blockIdx.x, A.ntiles * A.frames)
-                     : A.xcd_off == 1      ? (int)blockIdx.x
-                                           : xcd_remap(blockIdx.x, A.ntiles * A.frames);
+    // frame 116 at M = 894k 251.5-252.6 vs 263.9-264.6, trained 50k equal)
+    int tile = xcd_runs<16>(blockIdx.x, A.ntiles * A.frames);
     if (A.frames > 1) {  // batched frames: this block's frame and tile
         const int b = tile / A.ntiles;
         tile -= b * A.ntiles;
@@ -880,7 +843,7 @@ raster_sum_fwd_kernel(SumFwdArgs A) {
         A.stamps[8 * (size_t)tile] = t0;
         A.stamps[8 * (size_t)tile + 5] = n_all;
     }
-    const bool sparse = kMode == kModeSparse || kMode == kModeSparseStamp || kMode == kModeSparsePrio ||
+    const bool sparse = kMode == kModeSparse || kMode == kModeSparseStamp ||
                         kMode == kModeSparseIds ||
                         ((kMode == kModeAdaptive || kMode == kModeStamp) && n <= A.sparse_max);
     if (n == 0) seg_rec = nullptr;
@@ -939,7 +902,7 @@ raster_sum_fwd_kernel(SumFwdArgs A) {
 // but 4.3 us between the projection's end and its start (the frame no
 // faster); two with XCD runs of 16 tiles instead of pairs: equal.  K tiles
 // per wave with every tile's loads issued before the first blends (K = 2, 4):
-// slower (12.7 vs 12.0 us; 4: 26 vs 20 us per frame).  A/B knob 38 = 1: the
+// slower (12.7 vs 12.0 us; 4: 26 vs 20 us per frame).  GSVC_KNOB_GENERIC_RENDER = 1: the
 // generic kernel.
 template <int W, bool kSplit>
 __global__ __launch_bounds__(64 * W, 8) void raster_render_ids_kernel(SumFwdArgs A) {
@@ -1032,9 +995,8 @@ __host__ __device__ inline VStrides hwc_strides(unsigned img_w) {
 // implies -- an entry past a pixel's last contributor fails the alpha test
 // there in the same op sequence -- so nothing is read.  Entries past the tile's
 // 256th are skipped as there (final_idx < range.x + 256).
-// Round 4's entry-per-thread kernel (each thread looping over E pixels with
-// the skip, 9 block reductions per entry) is raster_sum_bwd_kernel_r4 below,
-// in the diagnostic library only (A/B knob 29 = 1).
+// (Round 4's entry-per-thread kernel -- each thread looping over E pixels with
+// the skip, 9 block reductions per entry -- lost to this one and is gone.)
 constexpr int kSBChunk = 64;
 constexpr int kSBThreads = 128;
 struct SumBwdLds {
@@ -1271,151 +1233,6 @@ __global__ __launch_bounds__(kSBThreads, 8) void raster_sum_bwd_kernel(
     }
 }
 
-#ifdef GSVC_DIAG
-// Round 4's op-path backward (diagnostic library, A/B knob 29 = 1): one
-// 256-thread workgroup per tile, entry-parallel (below).
-__global__ __launch_bounds__(256) void raster_sum_bwd_kernel_r4(
-    int tbx, int img_w, int img_h, int ntiles, const int *__restrict__ ids,
-    const int2 *__restrict__ bins, const float2 *__restrict__ xys, const float *__restrict__ conics,
-    const float *__restrict__ colors, const float *__restrict__ opac,
-    const int *__restrict__ final_idx, const float *__restrict__ v_out, VStrides vs,
-    float *__restrict__ grad, const int *__restrict__ det_off, const int *__restrict__ det_radii,
-    float *__restrict__ det_part, long long det_cap) {
-    __shared__ float4 s_pix[kTilePix];  // v_out rgb, final_idx bits
-    __shared__ float4 s_geo[kTilePix];  // x, y, a, b
-    __shared__ float4 s_col[kTilePix];  // c, opacity, r, g
-    __shared__ float s_blu[kTilePix];
-    __shared__ int s_gid[kTilePix];
-    __shared__ float s_red[9][kTilePix];
-    __shared__ int s_max[4];
-    const int tile = xcd_remap(blockIdx.x, ntiles);
-    const int ty = tile / tbx, tx = tile - ty * tbx;
-    const int tid = threadIdx.x;
-    const int pi = ty * kTile + (tid >> 4), pj = tx * kTile + (tid & 15);
-    const bool inside = pi < img_h && pj < img_w;
-    float4 pd = make_float4(0.f, 0.f, 0.f, __int_as_float(-2147483647 - 1));
-    if (inside) {
-        const size_t p = (size_t)pi * (size_t)img_w + (size_t)pj;
-        const float *v = v_out + (long long)pi * vs.h + (long long)pj * vs.w;
-        pd = make_float4(v[0], v[vs.c], v[2 * vs.c], __int_as_float(final_idx[p]));
-    }
-    s_pix[tid] = pd;
-    int f = __float_as_int(pd.w);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) f = max(f, __shfl_xor(f, off, 64));
-    if ((tid & 63) == 0) s_max[tid >> 6] = f;
-    __syncthreads();
-    const int maxf = max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3]));
-    const int2 range = bins[tile];
-    const int kend = min(range.y, maxf == (-2147483647 - 1) ? maxf : maxf + 1);
-    const float tx0 = (float)(tx * kTile), ty0 = (float)(ty * kTile);
-
-    for (int cs = range.x; cs < kend; cs += kTilePix) {
-        const int n = min(kTilePix, kend - cs);
-        if (tid < n) {
-            const int g = ids[cs + tid];
-            s_gid[tid] = g;
-            const float2 xy = xys[g];
-            s_geo[tid] = make_float4(xy.x, xy.y, conics[3 * g], conics[3 * g + 1]);
-            s_col[tid] = make_float4(conics[3 * g + 2], opac[g], colors[3 * g], colors[3 * g + 1]);
-            s_blu[tid] = colors[3 * g + 2];
-        }
-        __syncthreads();
-        const int lg = ceil_log2(n);
-        const int E = 1 << lg;
-        const int e = tid & (E - 1);
-        const int p_begin = (tid >> lg) << lg;  // E pixels per group
-        float a_r = 0.f, a_g = 0.f, a_b = 0.f, a_c0 = 0.f, a_c1 = 0.f, a_c2 = 0.f;
-        float a_x = 0.f, a_y = 0.f, a_o = 0.f;
-        if (e < n) {
-            const int k = cs + e;
-            const float4 G = s_geo[e];
-            const float4 C = s_col[e];
-            const float bl = s_blu[e];
-            const float ha = 0.5f * G.z, hc = 0.5f * C.x;
-            for (int pp = 0; pp < E; ++pp) {
-                const int p = p_begin + pp;
-                const float4 P = s_pix[p];
-                if (k > __float_as_int(P.w)) continue;
-                const float dx = G.x - (tx0 + (float)(p & 15));
-                const float dy = G.y - (ty0 + (float)(p >> 4));
-                const float s = splat_sigma_h(ha, G.w, hc, dx, dy);
-                const float vis = exp_neg(s);
-                const float al = fminf(1.0f, C.y * vis);
-                if (s < 0.0f || al < kAlphaMin) continue;
-                const float v_alpha = fmaf(bl, P.z, fmaf(C.w, P.y, C.z * P.x));
-                const float v_sigma = (-C.y * vis) * v_alpha;
-                a_r = fmaf(al, P.x, a_r);
-                a_g = fmaf(al, P.y, a_g);
-                a_b = fmaf(al, P.z, a_b);
-                const float hs = 0.5f * v_sigma;
-                const float hsdx = hs * dx;
-                a_c0 = fmaf(hsdx, dx, a_c0);
-                a_c1 = fmaf(hsdx, dy, a_c1);
-                a_c2 = fmaf(hs * dy, dy, a_c2);
-                a_x = fmaf(v_sigma, fmaf(G.z, dx, G.w * dy), a_x);
-                a_y = fmaf(v_sigma, fmaf(G.w, dx, C.x * dy), a_y);
-                a_o = fmaf(vis, v_alpha, a_o);
-            }
-        }
-        // combine the 256/E pixel groups of each entry
-        if (E < 64) {
-            for (int off = 32; off >= E; off >>= 1) {
-                a_r += __shfl_xor(a_r, off, 64);
-                a_g += __shfl_xor(a_g, off, 64);
-                a_b += __shfl_xor(a_b, off, 64);
-                a_c0 += __shfl_xor(a_c0, off, 64);
-                a_c1 += __shfl_xor(a_c1, off, 64);
-                a_c2 += __shfl_xor(a_c2, off, 64);
-                a_x += __shfl_xor(a_x, off, 64);
-                a_y += __shfl_xor(a_y, off, 64);
-                a_o += __shfl_xor(a_o, off, 64);
-            }
-        }
-        const int S = E < 64 ? 64 : E;
-        if (E >= 64 || (tid & 63) < E) {
-            s_red[0][tid] = a_x;
-            s_red[1][tid] = a_y;
-            s_red[2][tid] = a_c0;
-            s_red[3][tid] = a_c1;
-            s_red[4][tid] = a_c2;
-            s_red[5][tid] = a_r;
-            s_red[6][tid] = a_g;
-            s_red[7][tid] = a_b;
-            s_red[8][tid] = a_o;
-        }
-        __syncthreads();
-        if (tid < n) {
-            const int reps = kTilePix / S;
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                float v = s_red[c][tid];
-                for (int j = 1; j < reps; ++j) v += s_red[c][tid + j * S];
-                s_red[c][tid] = v;
-            }
-        }
-        __syncthreads();
-        // 16 lanes per entry, 9 of them add one float each into the splat's
-        // 64-byte gradient record: one memory request per (splat, tile).
-        for (int q = tid; q < n * 16; q += kTilePix) {
-            const int e2 = q >> 4, c = q & 15;
-            if (c >= 9) continue;
-            if (det_off) {
-                const int tby = (img_h + kTile - 1) / kTile;
-                const long long slot = det_slot(det_off, xys, det_radii, s_gid[e2], tx, ty, tbx, tby);
-                if (slot < det_cap) {
-                    det_part[9 * slot + c] = s_red[c][e2];
-                    continue;
-                }
-            }
-            unsafeAtomicAdd(grad + (size_t)s_gid[e2] * 16 + c, s_red[c][e2]);
-        }
-        __syncthreads();
-    }
-}
-
-#endif
-
 // Deterministic backward: splat i's record = its slots summed in bbox order +
 // the atomics of slots past det_cap (zero unless the capacity was short).
 __global__ __launch_bounds__(256) void det_gather_kernel(int n, const int *__restrict__ off,
@@ -1473,7 +1290,7 @@ __global__ __launch_bounds__(kProjThreads) void tile_insert_ids_kernel(
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
             hits = slab_insert_pairs<8>(c.x, c.y, r, tbx, tby, z, z,
                                         make_float4(0.f, __int_as_float(i), 0.f, 0.f), counts,
-                                        nullptr, 0, ids, ids_cap);
+                                        nullptr, ids, ids_cap);
         }
     }
     add_hits(hits, s_hits, m_acc);
@@ -1508,7 +1325,7 @@ __global__ __launch_bounds__(kThr) void tile_insert_ids_ordered_kernel(
     int *__restrict__ ids, int *__restrict__ m_acc, int *__restrict__ m_clear,
     float4 *__restrict__ rec_zero, unsigned *__restrict__ key, int *__restrict__ key_id,
     unsigned key_invisible, const float *__restrict__ conics, const float *__restrict__ colors,
-    const float *__restrict__ opac, float4 *__restrict__ rec, int scatter, int ids_cap) {
+    const float *__restrict__ opac, float4 *__restrict__ rec, int ids_cap) {
     __shared__ int s_hits[kThr / 64];
     __shared__ unsigned s_cnt[kAggWin];
     __shared__ int s_box[4][kThr / 64];
@@ -1524,9 +1341,8 @@ __global__ __launch_bounds__(kThr) void tile_insert_ids_ordered_kernel(
     unsigned x0 = 0, y0 = 0, x1 = 0, y1 = 0;
     // the gradient records' zeroing, the 48-byte records and the strip keys go
     // by position t, not by the ordered id i: every id in [0, n) is some t's,
-    // and the stores are coalesced (A/B knob 32 = 1: at i, scattered)
-    const bool by_pos = !(kDiag && scatter);
-    if (by_pos && t < n) {
+    // and the stores are coalesced (at i they would scatter)
+    if (t < n) {
         if (rec_zero) {
             const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -1540,21 +1356,11 @@ __global__ __launch_bounds__(kThr) void tile_insert_ids_ordered_kernel(
         }
     }
     if (have) {
-        if (!by_pos && rec_zero) {
-            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) rec_zero[4 * (size_t)i + q] = z;
-        }
         const int r = radii[i];
         const float2 c = xys[i];
         S.P.xy = c;
         S.P.rad = r;
         if (r > 0) tile_bbox(c.x, c.y, (float)r, tbx, tby, x0, y0, x1, y1);
-        if (!by_pos && rec) pack_record(i, xys, conics, colors, opac, rec);
-        if (!by_pos && key) {
-            key[i] = strip_key(c.x, c.y, r, tbx, tby, key_invisible);
-            key_id[i] = i;
-        }
     }
     // every lane of the block (block-uniform control flow inside)
     const int hits = slab_insert_window<kThr>(S, x0, y0, x1, y1, tbx, tby, counts, nullptr, s_cnt,
@@ -1595,20 +1401,19 @@ static OpOrderWs op_order_ws(char *base, int n) {
 }
 
 bool sum_forward_dense(int density_hint, int ntiles, int frames) {
-    if (knob(0) != 0) return knob(0) != kModeSparse;  // a forced kernel mode (A/B): no id slabs
+    // a forced kernel mode (A/B): no id slabs
+    if (knob(GSVC_KNOB_FWD_MODE) != 0) return knob(GSVC_KNOB_FWD_MODE) != kModeSparse;
     return (long long)density_hint > (long long)kDenseEntriesPerTile * ntiles * frames;
 }
 
 void sum_fwd_args_init(SumFwdArgs &A) {
     A = SumFwdArgs{};
-    A.sparse_max = knob(3) > 0 ? knob(3) : 8;
-    // A/B knob 10: speculative slab records per tile (default all kHeadSlots)
-    A.spec_slots = knob(10) > 0 && knob(10) < kHeadSlots ? knob(10) : kHeadSlots;
-    A.group_min = knob(15) > 0 ? knob(15) - 1 : kGroupMinDefault;
-    A.cut = knob(19) != 1;
+    A.sparse_max = knob(GSVC_KNOB_SPARSE_MAX) > 0 ? knob(GSVC_KNOB_SPARSE_MAX) : 8;
+    A.spec_slots = kHeadSlots;
+    A.group_min = knob(GSVC_KNOB_GROUP_MIN) > 0 ? knob(GSVC_KNOB_GROUP_MIN) - 1 : kGroupMinDefault;
+    A.cut = knob(GSVC_KNOB_NO_SIGMA_CUT) != 1;
     A.ids_cap = kTilePix;
-    A.xcd_off = knob(37);
-    A.ablate = knob(36);
+    A.ablate = knob(GSVC_KNOB_SPARSE_ABLATE);
     A.layout = kLayoutHWC;
     A.frames = 1;
 }
@@ -1628,11 +1433,9 @@ int sum_forward_launch(SumFwdArgs &A, int density_hint, hipStream_t s) {
     A.vec = (A.img_w % 4 == 0) && (((uintptr_t)A.out & 15) == 0) &&
             (((uintptr_t)A.final_idx & 15) == 0) && (((uintptr_t)A.final_Ts & 15) == 0);
     A.vec_chw = A.vec && (((size_t)A.img_w * (size_t)A.img_h) % 4 == 0);
-    A.store_policy = knob(7);  // kStoreNtSc1 unless an A/B run selects another (knob 7)
     const int ntiles = A.ntiles;
-    int mode = knob(0);
+    int mode = knob(GSVC_KNOB_FWD_MODE);
     if (mode == 0) mode = sum_forward_dense(density_hint, ntiles, A.frames) ? kModeBanded : kModeSparse;
-    if (knob(17) == 1 && mode == kModeSparse) mode = kModeSparsePrio;  // A/B knob 17
     // id slabs without final_idx (the render; the op path's forward, whose
     // backward needs no final_idx): the one-wave id-slab instance, or the
     // banded kernel for a dense op-path frame
@@ -1653,12 +1456,12 @@ int sum_forward_launch(SumFwdArgs &A, int density_hint, hipStream_t s) {
                                : raster_sum_fwd_kernel<kModeBanded, false>,
                    grid, dim3(128), s, tev, A);
     } else if (mode == kModeSparseIds) {
-        if (kDiag && knob(39) == 1 && A.frames == 1) A.stamps = reinterpret_cast<long long *>(debug_ptr());
-        // the single-frame render: two one-tile waves per workgroup (A/B knob 38 = 1:
-        // the generic kernel)
+        if (kDiag && knob(GSVC_KNOB_RENDER_STAMPS) == 1 && A.frames == 1) A.stamps = reinterpret_cast<long long *>(debug_ptr());
+        // the single-frame render: two one-tile waves per workgroup
+        // (GSVC_KNOB_GENERIC_RENDER = 1: the generic kernel)
         const bool render = A.frames == 1 && !A.bins_out && !A.final_idx && A.m_dev &&
                             A.ids_cap == kCarryCap && A.layout == kLayoutCHWClamped && A.rec && A.sort_ids;
-        if (render && knob(38) != 1) {
+        if (render && knob(GSVC_KNOB_GENERIC_RENDER) != 1) {
             // more than 8 entries per tile on average: the split-loop instance
             if ((long long)density_hint > 8ll * A.ntiles)
                 launch_fwd(raster_render_ids_kernel<2, true>, dim3((A.ntiles + 1) / 2), dim3(128), s, tev, A);
@@ -1694,11 +1497,6 @@ int sum_forward_launch(SumFwdArgs &A, int density_hint, hipStream_t s) {
                 A.stamps = reinterpret_cast<long long *>(debug_ptr());
                 launch_fwd(A.final_idx ? raster_sum_fwd_kernel<kModeSparseStamp, true> : raster_sum_fwd_kernel<kModeSparseStamp, false>, grid,
                            dim3(64), s, tev, A);
-                break;
-            case kModeSparsePrio:
-                launch_fwd(A.final_idx ? raster_sum_fwd_kernel<kModeSparsePrio, true>
-                                       : raster_sum_fwd_kernel<kModeSparsePrio, false>,
-                           grid, dim3(64), s, tev, A);
                 break;
             default:
                 return set_error(GSVC_ERR_ARG, "rasterize_sum_forward: unknown kernel mode %d", mode);
@@ -1808,7 +1606,7 @@ static int forward_slabs_impl(
                            gaussian_ids, m_slots + par, m_slots + (par ^ 1),
                            (float4 *)grad_records_zero, refresh ? ow.okey : nullptr,
                            refresh ? ow.okey_id : nullptr, strip_key_invisible(tbx, tby), conics,
-                           colors, opacities, ow.rec, knob(32), ids_cap);
+                           colors, opacities, ow.rec, ids_cap);
     } else if (num_points > 0) {
         hipLaunchKernelGGL(tile_insert_ids_kernel, dim3(ceil_div(num_points, kProjThreads)),
                            dim3(kProjThreads), 0, s, num_points, (const float2 *)xys, radii, tbx,
@@ -1887,8 +1685,7 @@ extern "C" int gsvc_rasterize_sum_forward_slabs_ordered(
 }
 
 // The op-path backward's launch (every backward entry point): the row-item
-// kernel, timed on channel kTimingSumBwd; the diagnostic library's knob 29 = 1
-// launches round 4's kernel instead (A/B).
+// kernel, timed on channel kTimingSumBwd.
 static void sum_bwd_launch(hipStream_t s, int tbx, int img_w, int img_h, int ntiles,
                            const int *ids, const int2 *bins, const float2 *xys, const float *conics,
                            const float *colors, const float *opac, const int *final_idx,
@@ -1896,15 +1693,6 @@ static void sum_bwd_launch(hipStream_t s, int tbx, int img_w, int img_h, int nti
                            const int *det_radii, float *det_part, long long det_cap, int flags = 0) {
     hipEvent_t tev[2];
     const int tslot = timing_begin(s, tev, kTimingSumBwd);
-#ifdef GSVC_DIAG
-    if (knob(29) == 1) {
-        launch_timed(raster_sum_bwd_kernel_r4, dim3(ntiles), dim3(256), 0, s, tev, tbx, img_w, img_h,
-                     ntiles, ids, bins, xys, conics, colors, opac, final_idx, v_out, vs, grad, det_off,
-                     det_radii, det_part, det_cap);
-        timing_end(s, tslot, kTimingSumBwd);
-        return;
-    }
-#endif
     // the deterministic slots always carry all 9 sums (det_gather reads them)
     const bool opac_grad = !(flags & GSVC_BWD_NO_OPACITY) || det_off;
     auto k = final_idx ? (opac_grad ? raster_sum_bwd_kernel<true, true> : raster_sum_bwd_kernel<true, false>)

@@ -55,10 +55,13 @@ struct TrainTileArgs {
     const float *gt;  // [3, H, W]
     float *grad;      // [N, 16]: v_xy 0:2, v_conic 2:5, v_colors 5:8, v_opacity 8
     float2 *err;      // [ntiles]: sum of squared, sum of absolute errors
-    int brun;         // band kernel: a rectangle row wider than this is two work items
-    int spec;         // band kernel: slab records loaded with the count
-    int grouped;      // band kernel forward: lane-group entry lists (A/B knob 14 = 1: off)
-    int diag;         // diagnostic knob 13 (timing experiments only; wrong results):
+    // unused[]: the words of four retired A/B arguments.  The argument layout is
+    // kept because the band kernel's code follows it: without these words the
+    // deterministic carry instance spills 18 SGPRs instead of 8 (kernel resource
+    // remarks; moving the live fields instead changed all four instances).
+    int unused0[2];
+    int grouped;      // band kernel forward: lane-group entry lists (GSVC_KNOB_TILE_NO_GROUPS = 1: off)
+    int diag;         // GSVC_KNOB_TILE_ABLATE (timing experiments only; wrong results):
                       // bits 2 no backward, 4 no forward
                       // blending, 8 no backward pixel work, 16 no run sums, 32 no atomics;
                       // 64 (A/B, exact): items in entry order, not longest first;
@@ -74,8 +77,7 @@ struct TrainTileArgs {
     const int *det_off;
     float4 *det_part;
     long long det_cap;
-    int prio;  // raise the wave priority over the order phase (s_setprio; knob 16 = 1 off)
-    int xcd_off;  // diagnostic A/B (knob 37): 1 dispatch order, 4 xcd_remap ranges
+    int unused1[2];
     // GSVC_TRAIN_CARRY (band kernel): the tile's candidates are the splat ids
     // cids[tile][0, counts[tile]) -- a superset of its entries carried from
     // step to step (train_splat_kernel) -- and an entry is a candidate whose
@@ -84,7 +86,9 @@ struct TrainTileArgs {
     // csorted[tile]: how many leading cids are in id order (a rebuild zeroes it,
     // the splat kernel's appends leave it behind the count); a tile of <= 64
     // whose cids are all sorted ranks its entries by one ballot, and one that
-    // is not sorts them, writes them back and sets it
+    // is not sorts them, writes them back and sets it.
+    // Never NULL with carried bins; the kernel's null checks stay (removing
+    // them is a change of the band kernel's code, left to its rewrite).
     int *cids;
     const uint2 *cbox;
     int *m_clear;
@@ -129,7 +133,7 @@ __device__ int block_brute_ids(const TrainTileArgs &A, int tx, int ty, int *s_gi
     return min(written, kT);
 }
 
-// Diagnostic only (gsvc_debug_set(5, 2) with gsvc_debug_set_ptr): s_memrealtime
+// Diagnostic only (GSVC_KNOB_STAMP = 2 with gsvc_debug_set_ptr): s_memrealtime
 // stamps per tile by thread 0 -- start, staged, forward done, scan done,
 // items done, end -- as int64[8].
 __device__ __forceinline__ long long tstamp() {
@@ -447,17 +451,12 @@ __global__ __launch_bounds__(256, 8) void train_tile_kernel(TrainTileArgs A) {
 // not formed.
 constexpr int kBSpec = 32;    // slab slots loaded with the count (64: slower, measured)
 constexpr int kBChunk = 64;   // entries staged at a time
-// rows wider than this split into two work items (A/B knob 11).  16 = never:
+// rows wider than this split into two work items.  16 = never:
 // measured 51.6 vs 54.0 us (10) at trained density, 31.8 vs 32.1 at init --
 // fewer rounds of segmented sums beat the longer pixel loops once items are
 // laid out by length (tools/item_sim.py models it)
 constexpr int kBRun = 16;
 constexpr int kBThreads = 128;
-// The band kernel's speculative slab records and work-item split width: the
-// constants in the product library, A/B knobs 12 / 11 in the diagnostic one.
-__device__ __forceinline__ int spec_of(const TrainTileArgs &A) { return kDiag ? A.spec : kBSpec; }
-__device__ __forceinline__ int brun_of(const TrainTileArgs &A) { return kDiag ? A.brun : kBRun; }
-
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 // raster_sum.hip blend_pair at opacity 1 (no index tracking): one splat
@@ -617,6 +616,7 @@ __device__ __forceinline__ void publish_loss(const float2 *err, int ntiles, doub
 template <int kThreads>
 __device__ int wg_sorted_members(const int *cand, int n, const uint2 *cbox, unsigned tx,
                                  unsigned ty, int *s_out, unsigned *bm, int *s_misc) {
+    static_assert(kThreads == 128, "the s_misc exchange is between two waves (BandLds::misc is int[4])");
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     constexpr int kPer = kTrainCarryCap / kThreads, kQ = 4, kR = 4;
     static_assert(kPer <= 32 && kPer % kQ == 0 && kPer % kR == 0, "membership mask layout");
@@ -703,16 +703,14 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     // grows from 2.6 us for the first workgroups of a CU to 11.7 us for its
     // 13th-16th, profiles/r03/stamps).  Raised over the order phase, a young
     // tile gets its round trips going while its elders compute.
-    if (!kDiag || A.prio) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(3);
     // runs of 16 tiles dealt over the XCDs: dense content (a textured frame's
     // objects) spread over all eight instead of loading the one or two whose
     // contiguous range covers them (tile kernel 273.7 -> 238.7 us on the
     // textured video's frame 116, unchanged on the bench's frame).
-    // A/B knob 37: 1 dispatch order, 4 contiguous ranges (runs of 4, 8 and 32
-    // were measured, round 5: within the dense frame's spread, not kept)
-    const int tile = !(kDiag && A.xcd_off) ? xcd_runs<16>(blockIdx.x, A.ntiles)
-                     : A.xcd_off == 1      ? (int)blockIdx.x
-                                           : xcd_remap(blockIdx.x, A.ntiles);
+    // (Runs of 4, 8 and 32 were measured, round 5: within the dense frame's
+    // spread, not kept.)
+    const int tile = xcd_runs<16>(blockIdx.x, A.ntiles);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     long long *st = kStamp ? A.stamps + 8 * (size_t)tile : nullptr;
     if (kStamp && tid == 0) st[0] = tstamp();
@@ -738,9 +736,9 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     int cid = 0;  // carried bins: the lane's candidate id
     int *tcids = carry ? A.cids + (size_t)tile * kTrainCarryCap : nullptr;
     if (carry) {
-        cid = tcids[tid < spec_of(A) ? tid : 0];
+        cid = tcids[tid < kBSpec ? tid : 0];
     } else {
-        const float4 *h0 = slab_rec(A.slab, A.ntiles, tile, tid < spec_of(A) ? tid : 0);
+        const float4 *h0 = slab_rec(A.slab, A.ntiles, tile, tid < kBSpec ? tid : 0);
         r0 = h0[0];
         r1 = h0[1];
         r2 = h0[2];
@@ -785,7 +783,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         // <= 64 candidates: wave 0 gathers their records and boxes by id, keeps
         // the tile's entries and ranks them by id (the others rank last)
         if (w == 0) {
-            if (lane >= spec_of(A) && lane < n) cid = tcids[lane];
+            if (lane >= kBSpec && lane < n) cid = tcids[lane];
             bool mem = false;
             if (lane < n) {
                 const uint2 b = A.cbox[cid];
@@ -841,7 +839,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             if (lane == 0) S.nsel = nm;
         }
     } else if (!dense) {
-        if (tid >= spec_of(A) && tid < n) {
+        if (tid >= kBSpec && tid < n) {
             const float4 *h = slab_rec(A.slab, A.ntiles, tile, tid);
             r0 = h[0];
             r1 = h[1];
@@ -910,7 +908,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     }
     __syncthreads();
     if (carry && (!dense || brute)) n = S.nsel;
-    if (!kDiag || A.prio) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     if (kStamp && tid == 0) st[1] = tstamp();
 
     // 2. forward: this wave's band against the entries that can reach it
@@ -1158,8 +1156,8 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                 const int ry0 = max((int)((rc >> 8) & 15u), y_lo), ry1 = min((int)((rc >> 12) & 15u), y_hi);
                 const int rw = (int)((rc >> 4) & 15u) - (int)(rc & 15u) + 1;
                 if (ry0 <= ry1) {
-                    items = (ry1 - ry0 + 1) * (rw > brun_of(A) ? 2 : 1);
-                    ilen = rw > brun_of(A) ? (rw + 1) >> 1 : rw;
+                    items = (ry1 - ry0 + 1) * (rw > kBRun ? 2 : 1);
+                    ilen = rw > kBRun ? (rw + 1) >> 1 : rw;
                 }
             }
         }
@@ -1224,7 +1222,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                 const int j = item - eoff;  // item index within the entry
                 const int rx0 = (int)(ro & 15u), rx1 = (int)((ro >> 4) & 15u);
                 const int rwid = rx1 - rx0 + 1;
-                const int ipr = rwid > brun_of(A) ? 2 : 1;
+                const int ipr = rwid > kBRun ? 2 : 1;
                 const int jr = ipr == 1 ? j : (j >> 1);
                 const int row = max((int)((ro >> 8) & 15u), y_lo) + jr;
                 const int half = (rwid + 1) >> 1;
@@ -1319,14 +1317,10 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                 // (2.9x slower kernel: the LDS serialises an entry's items); a
                 // packed two-pixel loop (80 VGPRs, 6 waves per SIMD: 64.0 vs 58.5
                 // us).  An entry has at most 8 items in a band unless rows split
-                // in two (brun < 16): runs of <= 8 lanes need no row_shr:8 step (a
+                // in two (kBRun < 16): runs of <= 8 lanes need no row_shr:8 step (a
                 // run crossing a 16-lane row still takes the row broadcast)
-                if (!(kDiag && (A.diag & 16))) {  // diag 16: no run sums (wrong)
-                    if (brun_of(A) < 16)
-                        wave_seg_sums<8, true>(g, own);
-                    else
-                        wave_seg_sums<8, false>(g, own);
-                }
+                if (!(kDiag && (A.diag & 16)))  // diag 16: no run sums (wrong)
+                    wave_seg_sums<8, (kBRun < 16)>(g, own);
                 const int own_next = __shfl_down(own, 1, 64);
                 if (item < total && (lane == 63 || item + 1 == total || own_next != own)) {
 #pragma unroll
@@ -1399,7 +1393,7 @@ struct TrainSplatArgs {
     // frame (rec, xys, radii, its tile box cbox; its gradient record zeroed)
     // and, when the box leaves the hull of the boxes it was binned under
     // (chull), appends its id to the tiles the grown hull adds (cids, ccount);
-    // its box area goes into the next frame's M (m_next)
+    // a wave with insertions sets the next frame's M (m_next) to 1
     int carry, tbx, tby;
     float2 *xys;
     uint2 *cbox, *chull;
@@ -1496,7 +1490,7 @@ __device__ __forceinline__ void st_row(float *base, int i, const float *in) {
     }
 }
 
-// Diagnostic (gsvc_debug_set(5, 4) with gsvc_debug_set_ptr): s_memrealtime
+// Diagnostic (GSVC_KNOB_STAMP = 4 with gsvc_debug_set_ptr): s_memrealtime
 // stamps per wave by lane 0 -- start, operands landed, Adan stores issued,
 // carry done, M added, stores acknowledged -- as int64[8] at st.
 __device__ __forceinline__ void splat_stamp(long long *st, int k) {
@@ -1859,8 +1853,10 @@ __device__ __forceinline__ int splat_step_split(const TrainSplatArgs &A, int bas
     return hits;
 }
 
-template <bool kStamp, int kBlock = 256>
-__global__ __launch_bounds__(kBlock) void train_splat_kernel(TrainSplatArgs A) {
+// 256 threads per workgroup (64, 128, 192 and 512 were measured and not kept:
+// DESIGN.md §6, profiles/r03/splat_wg/ and splat_wg2/).
+template <bool kStamp>
+__global__ __launch_bounds__(256) void train_splat_kernel(TrainSplatArgs A) {
     long long *st = kStamp ? A.stamps + 8 * (size_t)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6))
                            : nullptr;
     if (kStamp && (threadIdx.x & 63) == 0) st[0] = tstamp();
@@ -1868,27 +1864,24 @@ __global__ __launch_bounds__(kBlock) void train_splat_kernel(TrainSplatArgs A) {
         // the first workgroup (no splats): the loss; dispatched first so it
         // runs beside the splats
         __shared__ double s_l[2][4];
-        publish_loss<kBlock>(A.err, A.ntiles, A.inv_count, A.loss, A.loss_seq, A.det_off, A.n, s_l);
+        publish_loss<256>(A.err, A.ntiles, A.inv_count, A.loss, A.loss_seq, A.det_off, A.n, s_l);
         if (kStamp) splat_stamp(st, 5);
         return;
     }
     int hits;
-    if (!kStamp && kBlock == 256 && A.split) {
-        hits = splat_step_split(A, (blockIdx.x - 1) * (kBlock / 2));
+    if (!kStamp && A.split) {
+        hits = splat_step_split(A, (blockIdx.x - 1) * 128);
     } else {
         const int t = (blockIdx.x - 1) * blockDim.x + threadIdx.x;
         hits = t < A.n ? splat_step<kStamp>(A, t, st) : 0;
     }
-    if (A.carry == 2) {
+    if (A.carry) {
         // the next frame's M is read only as M >= 1 (the tile kernel's background
         // branch, rasterize_sum.py:121-127): one plain store of 1 per wave that
         // has tiles, instead of a per-workgroup device-scope atomic add -- those
         // all go to one address and serialise at the memory side (~5 us of the
         // kernel at 196 workgroups, ~20 us at 782)
         if (__ballot(hits > 0) != 0ull && (threadIdx.x & 63) == 0) *A.m_next = 1;
-    } else if (A.carry) {
-        __shared__ int s_hits[4];
-        add_hits(hits, s_hits, A.m_next);  // the next frame's M
     }
     if (kStamp) {
         if ((threadIdx.x & 63) == 0) st[4] = tstamp();
@@ -2102,23 +2095,15 @@ static int train_step_impl(int num_points, float *xyz, float *cholesky,
     T.grad = reinterpret_cast<float *>(w.grad);
     T.err = w.err;
     T.out = render_out;
-    // A/B knob 11: the band kernel's work-item split width (default kBRun)
-    T.brun = knob(11) >= 4 && knob(11) <= 16 ? knob(11) : kBRun;
-    // A/B knob 12: speculative slab records per tile (default kBSpec)
-    T.spec = knob(12) > 0 && knob(12) <= 64 ? knob(12) : kBSpec;
-    T.diag = knob(13);
-    T.grouped = knob(14) != 1;
-    T.prio = knob(16) != 1;  // A/B knob 16 = 1: no raised priority
-    T.xcd_off = knob(37);  // A/B: 1 dispatch order, 4 contiguous XCD ranges
+    T.diag = knob(GSVC_KNOB_TILE_ABLATE);
+    T.grouped = knob(GSVC_KNOB_TILE_NO_GROUPS) != 1;
     T.det_off = det_off;
     T.det_part = det_part;
     T.det_cap = det_capacity;
     if (carry) {
         T.cids = w.cids;
         T.cbox = w.cbox;
-        // (zeroed with ccount whenever the bins are rebuilt; A/B knob 28 = 1: no
-        // sorted lists -- every step ranks, nothing is written back)
-        T.csorted = knob(28) == 1 ? nullptr : w.csorted;
+        T.csorted = w.csorted;  // (zeroed with ccount whenever the bins are rebuilt)
     }
     // the tile kernel of the frame whose slots are fs
     auto launch_tiles = [&](const FrameSlots &fs) {
@@ -2127,13 +2112,13 @@ static int train_step_impl(int num_points, float *xyz, float *cholesky,
         T.m_dev = fs.m_acc;
         T.m_clear = carry ? fs.m_clear : nullptr;
         if constexpr (kDiag) {
-            if (knob(5) == 2 && debug_ptr() && !carry) {  // diagnostic: per-tile stamps
+            if (knob(GSVC_KNOB_STAMP) == 2 && debug_ptr() && !carry) {  // diagnostic: per-tile stamps
                 T.stamps = reinterpret_cast<long long *>(debug_ptr());
                 auto kfn = train_tile_kernel<true>;
                 hipLaunchKernelGGL(kfn, dim3(ntiles), dim3(kT), 0, s, T);
                 return check_launch("train_step_sum: tiles");
             }
-            if (knob(5) == 3 && debug_ptr()) {  // diagnostic: per-tile stamps, band kernel
+            if (knob(GSVC_KNOB_STAMP) == 3 && debug_ptr()) {  // diagnostic: per-tile stamps, band kernel
                 T.stamps = reinterpret_cast<long long *>(debug_ptr());
                 if (carry)
                     hipLaunchKernelGGL((train_tile_band_kernel<true, false, true>), dim3(ntiles),
@@ -2148,8 +2133,8 @@ static int train_step_impl(int num_points, float *xyz, float *cholesky,
         const int tslot = timing_begin(s, tev, kTimingTrainTile);
         bool launched = false;
         if constexpr (kDiag) {
-            // knob 8 = 1: the 256-thread workgroup-per-tile kernel (A/B; atomics only)
-            if (knob(8) == 1 && !det && !carry) {
+            // GSVC_KNOB_TILE_WG256: the 256-thread workgroup-per-tile kernel (A/B; atomics only)
+            if (knob(GSVC_KNOB_TILE_WG256) == 1 && !det && !carry) {
                 launch_timed(train_tile_kernel<false>, dim3(ntiles), dim3(kT), 0, s, tev, T);
                 launched = true;
             }
@@ -2201,8 +2186,7 @@ static int train_step_impl(int num_points, float *xyz, float *cholesky,
     P.err = w.err;
     P.loss = loss;
     if (carry && update) {
-        // 2: M as a flag (A/B knob 22 = 1: the exact count by atomics)
-        P.carry = knob(22) == 1 ? 1 : 2;
+        P.carry = 1;  // (the next frame's M as a flag, not the exact count)
         P.tbx = tbx;
         P.tby = tby;
         P.xys = (float2 *)w.f.xys;
@@ -2214,37 +2198,21 @@ static int train_step_impl(int num_points, float *xyz, float *cholesky,
     }
     P.loss_seq = loss_seq;
     // one extra (first) workgroup sums the loss, beside the splat workgroups
-    // A/B knob 21 = 64, 128, 192 or 512: other splat workgroup sizes
-    const int sb = knob(21) == 64 || knob(21) == 128 || knob(21) == 192 || knob(21) == 512
-                       ? knob(21)
-                       : 256;
-    // (1: the carry in the geometry wave; A/B knob 36 = 2: both waves project and
-    // share its stores -- measured equal, 9.92-10.0 vs 9.85-9.98 us, not kept;
-    // 3: the xyz elements on the colour wave)
-    // two waves per 64 splats (splat_step_split) unless A/B knob 34 = 1 or
-    // another workgroup size (nine lanes per splat, one per parameter element,
-    // was measured, round 6: 18.6 vs 10.5 us, profiles/r06/splat_elem/)
-    P.split = sb == 256 && knob(34) != 1 ? 1 : 0;
-    const int per_block = P.split ? sb / 2 : sb;
+    // two waves per 64 splats (splat_step_split: the carry in the geometry
+    // wave) unless GSVC_KNOB_SPLAT_ONE_LANE = 1 (nine lanes per splat, one per
+    // parameter element, was measured, round 6: 18.6 vs 10.5 us,
+    // profiles/r06/splat_elem/)
+    P.split = knob(GSVC_KNOB_SPLAT_ONE_LANE) != 1 ? 1 : 0;
+    const int per_block = P.split ? 128 : 256;
     const int blocks = (num_points > 0 ? ceil_div(num_points, per_block) : 0) + 1;
     hipEvent_t tev[2];
     const int tslot = timing_begin(s, tev, kTimingTrainSplat);
     bool launched = false;
     if constexpr (kDiag) {
-        launched = true;
-        if (knob(5) == 4 && debug_ptr()) {  // diagnostic: per-wave stamps of the splat kernel
+        if (knob(GSVC_KNOB_STAMP) == 4 && debug_ptr()) {  // diagnostic: per-wave stamps of the splat kernel
             P.stamps = reinterpret_cast<long long *>(debug_ptr());
             hipLaunchKernelGGL(train_splat_kernel<true>, dim3(ceil_div(num_points, 256) + 1), dim3(256), 0, s, P);
-        } else if (sb == 64) {
-            launch_timed(train_splat_kernel<false, 64>, dim3(blocks), dim3(64), 0, s, tev, P);
-        } else if (sb == 128) {
-            launch_timed(train_splat_kernel<false, 128>, dim3(blocks), dim3(128), 0, s, tev, P);
-        } else if (sb == 192) {
-            launch_timed(train_splat_kernel<false, 192>, dim3(blocks), dim3(192), 0, s, tev, P);
-        } else if (sb == 512) {
-            launch_timed(train_splat_kernel<false, 512>, dim3(blocks), dim3(512), 0, s, tev, P);
-        } else {
-            launched = false;
+            launched = true;
         }
     }
     if (!launched) launch_timed(train_splat_kernel<false>, dim3(blocks), dim3(256), 0, s, tev, P);

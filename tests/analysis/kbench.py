@@ -3,7 +3,7 @@
     python tests/analysis/kbench.py [--splats 10000 50000] [--variants 0 1] [--iters 200]
 
 Sets up a 1920x1080 frame (reference init distributions), bins it, then for
-each kernel variant (C-ABI knob gsvc_debug_set(0, v); 0 = automatic) captures ``iters``
+each kernel variant (C-ABI knob Knob.FWD_MODE = v; 0 = automatic) captures ``iters``
 back-to-back launches in a HIP graph and replays it, so host launch overhead
 cannot starve the GPU; prints average microseconds per launch and the
 algorithmic-bytes rate.  Outputs of every variant are checked bit-identical to
@@ -29,6 +29,7 @@ import torch  # noqa: E402
 
 from gsvc_amd import _lib as L  # noqa: E402
 from gsvc_amd import ops  # noqa: E402
+from gsvc_amd.knobs import Knob  # noqa: E402
 
 H, W = 1080, 1920
 
@@ -102,10 +103,9 @@ def main():
         sh = s["shape"]
         nbytes = 36 * sh["N_vis"] + 4 * sh["M_eff"] + 8 * sh["T"] + 16 * sh["P"]
         ref_out = ref_idx = None
-        lib.gsvc_debug_set(1, n)  # splat count for the packed-record experiment
         for v in list(args.variants) + [1000 + t for t in args.thresholds]:
-            lib.gsvc_debug_set(0, v if v < 1000 else 6)
-            lib.gsvc_debug_set(3, v - 1000 if v >= 1000 else 0)
+            lib.gsvc_debug_set(Knob.FWD_MODE, v if v < 1000 else 6)
+            lib.gsvc_debug_set(Knob.SPARSE_MAX, v - 1000 if v >= 1000 else 0)
             out = torch.empty((H, W, 3), device=s["dev"])
             idx = torch.empty((H, W), dtype=torch.int32, device=s["dev"])
             us = time_graph(lambda: L.call("gsvc_rasterize_sum_forward_ex", *fwd_args(s, out, idx)),
@@ -121,7 +121,7 @@ def main():
             results.append(rec)
             print(json.dumps(rec), flush=True)
         if args.stamps:
-            lib.gsvc_debug_set(0, 3)
+            lib.gsvc_debug_set(Knob.FWD_MODE, 3)
             out = torch.empty((H, W, 3), device=s["dev"])
             idx = torch.empty((H, W), dtype=torch.int32, device=s["dev"])
             st = torch.zeros((s["shape"]["T"], 4), dtype=torch.int64, device=s["dev"])
@@ -140,9 +140,9 @@ def main():
                        dense_tiles=int(w1.sum()),
                        wave1_dur=q((t[w1, 3] - t[w1, 2]) * 0.01) if w1.any() else None)
             print(json.dumps(rec), flush=True)
-            lib.gsvc_debug_set(0, 0)
+            lib.gsvc_debug_set(Knob.FWD_MODE, 0)
         if args.backward:
-            lib.gsvc_debug_set(0, 0)
+            lib.gsvc_debug_set(Knob.FWD_MODE, 0)
             out = torch.empty((H, W, 3), device=s["dev"])
             idx = torch.empty((H, W), dtype=torch.int32, device=s["dev"])
             L.call("gsvc_rasterize_sum_forward_ex", *fwd_args(s, out, idx))
@@ -155,8 +155,8 @@ def main():
                      frac=round(bb / us / 1e3 / 8000, 4), **sh)
             results.append(r)
             print(json.dumps(r), flush=True)
-    lib.gsvc_debug_set(0, 0)
-    lib.gsvc_debug_set(3, 0)
+    lib.gsvc_debug_set(Knob.FWD_MODE, 0)
+    lib.gsvc_debug_set(Knob.SPARSE_MAX, 0)
 
 
 if __name__ == "__main__":

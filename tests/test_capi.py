@@ -60,6 +60,58 @@ def test_product_library_has_no_diagnostics():
         assert variant in dnames, variant
 
 
+def _header_knobs():
+    """(enumerators of enum gsvc_knob, the "retired, never reuse" numbers) of
+    include/gsvc_amd_diag.h."""
+    src = open(DIAG_HEADER).read()
+    body = re.search(r"enum\s+gsvc_knob\s*\{(.*?)\};", src, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    live = {n: int(v) for n, v in re.findall(r"\bGSVC_KNOB_([A-Z0-9_]+)\s*=\s*(\d+)", body)}
+    note = re.search(r"Retired, never reuse(.*?)\*/", src, flags=re.S).group(1)
+    retired = [int(v) for v in re.findall(r"\d+", note.split(":", 1)[1])]  # the list after the colon
+    return live, retired
+
+
+def test_knob_enum_matches_header():
+    """gsvc_amd.knobs.Knob is enum gsvc_knob of include/gsvc_amd_diag.h, name by
+    name and value by value; live and retired numbers are disjoint and fill
+    [0, 40) without a number in both lists."""
+    from gsvc_amd.knobs import RETIRED, Knob
+    live, retired = _header_knobs()
+    assert live and {k.name: int(k) for k in Knob} == live
+    assert sorted(retired) == sorted(RETIRED) and len(set(retired)) == len(retired)
+    assert not set(retired) & set(live.values())
+    assert sorted(set(retired) | set(live.values())) == list(range(40))
+
+
+def test_debug_set_accepts_live_keys_only():
+    """gsvc_debug_set sets a live knob and returns its previous value; a
+    retired number, -1 and kKnobs = 40 return -1 (a stale tool stops)."""
+    from gsvc_amd import _lib
+    from gsvc_amd.knobs import RETIRED, Knob
+    lib = ctypes.CDLL(_lib.DIAG_LIB_PATH)
+    lib.gsvc_debug_set.argtypes = [ctypes.c_int, ctypes.c_int]
+    for k in Knob:
+        old = lib.gsvc_debug_set(k, 0)
+        assert old >= 0, k
+        assert lib.gsvc_debug_set(k, 7) == 0, k
+        assert lib.gsvc_debug_set(k, old) == 7, k  # restored
+        assert lib.gsvc_debug_set(k, old) == old, k
+    for k in (*RETIRED, -1, 40):
+        assert lib.gsvc_debug_set(k, 0) == -1, k
+
+
+def test_no_bare_knob_numbers_in_sources():
+    """Every knob read in the library's sources names its enumerator."""
+    import glob
+    bare = []
+    for path in sorted(glob.glob(os.path.join(REPO, "gsvc_amd", "csrc", "*"))):
+        for ln, line in enumerate(open(path, errors="replace"), 1):
+            if re.search(r"\bknob\(\s*\d", line):
+                bare.append(f"{os.path.basename(path)}:{ln}: {line.strip()}")
+    assert not bare, bare
+
+
 def test_abi_version_and_queries():
     from gsvc_amd import _lib
     lib = _lib.load()

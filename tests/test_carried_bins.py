@@ -14,6 +14,8 @@ overflow 256 (the bbox rebuild), and splats leaving / entering the image.
 import pytest
 import torch
 
+from gsvc_amd.knobs import Knob
+
 pytestmark = pytest.mark.gpu
 
 
@@ -82,9 +84,9 @@ def test_carried_fast_motion_and_overflow(cuda, deterministic, every):
     _same(a, b)
 
 
-@pytest.mark.parametrize("pair", [(34, 1)])
+@pytest.mark.parametrize("pair", [(Knob.SPLAT_ONE_LANE, 1)])
 def test_splat_kernel_layouts_bitwise(cuda, deterministic, pair):
-    """The splat kernel's layouts (train.hip): one lane per splat (knob 34 = 1)
+    """The splat kernel's layouts (train.hip): one lane per splat (Knob.SPLAT_ONE_LANE = 1)
     and the product's two waves with the carry in the geometry wave -- the same op
     sequence per element, so bitwise the same trajectory, deterministic
     partial sums included, through a bin rebuild."""

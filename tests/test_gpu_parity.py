@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import golden_names, knobs, load_golden
+from gsvc_amd.knobs import Knob
 
 pytestmark = pytest.mark.gpu
 
@@ -518,7 +519,7 @@ def test_render_frame_nonfinite_colours(cuda, oracle, mode):
     colors = _nonfinite_colours(z["colors"], np.random.default_rng(6))
     # the fixture's means2d / L / colours as the frame inputs (no tanh, zero bound)
     bound = torch.zeros(3, device="cuda")
-    with knobs((0, mode)):
+    with knobs((Knob.FWD_MODE, mode)):
         out = render_frame_sum(T(z["means2d"]), T(z["L"]), T(colors), H, W,
                                torch.ones(3, device="cuda"), xyz_tanh=False, cholesky_bound=bound)
     r = oracle.render_sum(z["means2d"], z["L"], colors, np.ones((len(colors), 1), np.float32), H, W)

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import golden_names, knobs, load_golden
+from gsvc_amd.knobs import Knob
 
 pytestmark = pytest.mark.gpu
 
@@ -231,7 +232,7 @@ def test_render_frame_matches_op_path(cuda, oracle, mode, case):
         n = 10000 if case.endswith("10k") else 50000
         means, L, colors, opac = oracle.synthetic_frame(n, seed=n + 1, rgb_w=2.0)
     bg = torch.ones(3, device="cuda")
-    with knobs((0, mode)):
+    with knobs((Knob.FWD_MODE, mode)):
         fast = render_sum_frame(T(means), T(L), T(colors), T(opac), H, W, _tb(H, W), bg)
     with torch.no_grad():
         ref = _op_path_frame(T(means), T(L), T(colors), T(opac), H, W, bg)
@@ -387,7 +388,7 @@ def test_render_frames_batch_matches_single(cuda, mode, H, W, sizes, cluster):
     bound = torch.tensor([0.5, 0.0, 0.5], device="cuda")
     rgbw = torch.rand(sum(sizes), 1, device="cuda") + 0.5
     bg = torch.tensor([0.3, 0.6, 0.9], device="cuda")
-    with knobs((0, mode)):
+    with knobs((Knob.FWD_MODE, mode)):
         outs = [render_frames_sum(xyz, chol, feat, sizes, H, W, bg, cholesky_bound=bound,
                                   rgb_w=rgbw) for _ in range(3)]  # parity slots reused
         off = 0

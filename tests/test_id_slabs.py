@@ -1,9 +1,9 @@
 """GPU suite: the single-frame render over 4-byte id slabs (the product
 default for sparse frames; raster_render_ids_kernel, two
-one-tile waves per workgroup, against the generic kernel: A/B knob 38 = 1)
+one-tile waves per workgroup, against the generic kernel: Knob.GENERIC_RENDER = 1)
 against the render over 48-byte
-slab records (A/B knob 24 = 1, diagnostic library) and the banded kernel
-(knob 0 = 2, records).  Same entries per tile, same id order, same blend: the
+slab records (Knob.RECORD_SLABS = 1, diagnostic library) and the banded kernel
+(Knob.FWD_MODE = 2, records).  Same entries per tile, same id order, same blend: the
 images must be bit-identical, including tiles past 256 entries (the id
 slabs: their first 256 ids rebuilt from the bboxes; the record slabs: sorted
 from the slab and its overflow ids up to 1024 entries, rebuilt past that), ragged image sizes and a frame with no
@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import knobs
+from gsvc_amd.knobs import Knob
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +49,7 @@ def test_id_slab_render_bit_identical(cuda, oracle, n, H, W, chol, cluster):
     got = []
     # records; banded; the order at any density; the generic one-wave kernel
     # instead of raster_render_ids_kernel
-    for pair in ((24, 1), (0, 2), (27, 1), (38, 1)):
+    for pair in ((Knob.RECORD_SLABS, 1), (Knob.FWD_MODE, 2), (Knob.KEEP_ORDER, 1), (Knob.GENERIC_RENDER, 1)):
         with knobs(pair):
             got += [render_frame_sum(xyz, c, f, H, W, bg, cholesky_bound=bound) for _ in range(3)]
     torch.cuda.synchronize()
@@ -88,7 +89,7 @@ def test_needle_splats_every_route(cuda, oracle):
     bg = torch.tensor([0.3, 0.6, 0.9], device=cuda)
     ref = render_frame_sum(xyz, c, f, H, W, bg, cholesky_bound=bound)
     got = []
-    for pair in ((24, 1), (0, 2), (0, 1), (38, 1)):  # records; banded; sparse records; generic kernel
+    for pair in ((Knob.RECORD_SLABS, 1), (Knob.FWD_MODE, 2), (Knob.FWD_MODE, 1), (Knob.GENERIC_RENDER, 1)):  # records; banded; sparse records; generic kernel
         with knobs(pair):
             got.append(render_frame_sum(xyz, c, f, H, W, bg, cholesky_bound=bound))
     torch.cuda.synchronize()
@@ -102,7 +103,7 @@ def test_needle_splats_every_route(cuda, oracle):
 
 
 def test_id_slab_batched_render_bit_identical(cuda):
-    """Batched frames (gsvc_render_frames_sum) over id slabs (A/B knob 25 = 1)
+    """Batched frames (gsvc_render_frames_sum) over id slabs (Knob.BATCH_ID_SLABS = 1)
     against the records: every frame's image bit-identical."""
     from gsvc_amd.render import render_frames_sum
     H, W = 270, 480
@@ -114,7 +115,7 @@ def test_id_slab_batched_render_bit_identical(cuda):
     bound = torch.tensor([0.5, 0.0, 0.5], device=cuda)
     bg = torch.ones(3, device=cuda)
     ref = render_frames_sum(xyz, chol, feat, sizes, H, W, bg, cholesky_bound=bound)
-    with knobs((25, 1)):
+    with knobs((Knob.BATCH_ID_SLABS, 1)):
         got = [render_frames_sum(xyz, chol, feat, sizes, H, W, bg, cholesky_bound=bound)
                for _ in range(3)]
     torch.cuda.synchronize()

@@ -3,13 +3,14 @@ only the entries whose alpha >= 1/255 rectangle reaches its 4x4-pixel block.
 Skipped pairs contribute nothing in the reference, so every variant must be
 bit-identical: lists always on / the default threshold / never, the sparse
 and banded composites, and the fused training step's forward with and
-without its lists (A/B knobs 15 and 14), at random-init and trained-like
+without its lists (Knob.GROUP_MIN and Knob.TILE_NO_GROUPS), at random-init and trained-like
 densities (3 to ~60 entries per tile)."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import knobs
+from gsvc_amd.knobs import Knob
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +31,10 @@ def test_composite_lists_bit_identical(cuda, oracle, n, chol):
     means, L, colors, opac = oracle.synthetic_frame(n, seed=n + 17, rgb_w=2.0, chol_scale=chol)
     bg = torch.ones(3, device="cuda")
     outs = {}
-    # mode 1 sparse / 2 banded; knob 15 = 1: lists on every chunk, 65: never
+    # mode 1 sparse / 2 banded; Knob.GROUP_MIN = 1: lists on every chunk, 65: never
     for mode in (1, 2):
         for lists in (0, 1, 65):
-            with knobs((0, mode), (15, lists)):
+            with knobs((Knob.FWD_MODE, mode), (Knob.GROUP_MIN, lists)):
                 outs[(mode, lists)] = render_sum_frame(T(means), T(L), T(colors), T(opac), H, W,
                                                        _tb(H, W), bg)
     ref = outs[(1, 65)]
@@ -57,7 +58,7 @@ def test_composite_lists_match_oracle_dense(cuda, oracle):
 @pytest.mark.parametrize("chol", [1.0, 4.0])
 def test_train_forward_lists_bit_identical(cuda, chol):
     """The fused step's render with the band kernel's lists (default) and
-    without (knob 14 = 1) is the same image; the gradients agree to the float
+    without (Knob.TILE_NO_GROUPS = 1) is the same image; the gradients agree to the float
     atomics' summation order."""
     from gsvc_amd.frame import make_frame_model, synthetic_gt
     gt = synthetic_gt(256, 384, 3, cuda)
@@ -66,7 +67,7 @@ def test_train_forward_lists_bit_identical(cuda, chol):
         model = make_frame_model(256, 384, 6000, cuda, seed=21)
         with torch.no_grad():
             model._cholesky.mul_(chol)
-        with knobs((14, knob)):
+        with knobs((Knob.TILE_NO_GROUPS, knob)):
             render = torch.empty(3, 256, 384, device=cuda)
             g = torch.empty(6000, 9, device=cuda)
             from gsvc_amd.train import train_step_sum
@@ -87,7 +88,7 @@ def _bits(t):
 @pytest.mark.parametrize("case", ["unit", "unit_dense", "mixed", "edge"])
 def test_composite_sigma_cut_bit_identical(cuda, oracle, case):
     """The sparse render's sigma-threshold blend (chunks whose entries all have
-    unit opacity, finite colour and bounded geometry; knob 19 = 1 turns it off)
+    unit opacity, finite colour and bounded geometry; Knob.NO_SIGMA_CUT = 1 turns it off)
     gives the same bits as the test as written -- including chunks that hold a
     NaN or infinite colour, an overflowing conic or a non-unit opacity, which
     must keep the written test (bitwise compare: NaN pixels included)."""
@@ -108,7 +109,7 @@ def test_composite_sigma_cut_bit_identical(cuda, oracle, case):
     bg = torch.ones(3, device="cuda")
     outs = []
     for knob in (0, 1):
-        with knobs((0, 1), (19, knob)):
+        with knobs((Knob.FWD_MODE, 1), (Knob.NO_SIGMA_CUT, knob)):
             outs.append(render_sum_frame(T(means), T(L), T(colors), T(opac), H, W, _tb(H, W), bg))
     assert torch.equal(_bits(outs[0]), _bits(outs[1])), case
     if case == "unit_dense":

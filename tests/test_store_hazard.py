@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from conftest import REPO, knobs
+from gsvc_amd.knobs import Knob
 
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import store_hazard_scan as S  # noqa: E402
@@ -120,8 +121,8 @@ def test_every_store_layout_matches_oracle_1080p(cuda, oracle, n):
             np.testing.assert_allclose(got, want, rtol=0, atol=1e-5, err_msg=name)
             checked.append(name)
     # the banded kernel: CHW planes with 8-byte stores, HWC rows (diagnostic
-    # library: knob 0 = 2 forces it; the product picks it past 96 entries per tile)
-    with knobs((0, 2)):
+    # library: Knob.FWD_MODE = 2 forces it; the product picks it past 96 entries per tile)
+    with knobs((Knob.FWD_MODE, 2)):
         for _ in range(3):
             np.testing.assert_allclose(render().cpu().numpy(), want_render, rtol=0, atol=1e-5,
                                        err_msg="render_chw_banded")

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import knobs
+from gsvc_amd.knobs import Knob
 
 
 def test_cpu_tensors_raise():
@@ -49,7 +50,7 @@ def _run(means, L, col, H, W, python_path, v_out):
         return out, xys, radii, conics, nth
 
     if python_path:
-        with knobs((0, 1)):  # the diagnostic library: the Python Functions over ctypes
+        with knobs((Knob.FWD_MODE, 1)):  # the diagnostic library: the Python Functions over ctypes
             res = go()
     else:
         res = go()
@@ -185,7 +186,7 @@ def test_cpp_functions_partial_gradients(cuda):
                     "depths": depths.sum() + (xys * w_xy).sum()}[which]
             loss.backward()
         if python_path:
-            with knobs((0, 1)):
+            with knobs((Knob.FWD_MODE, 1)):
                 go()
         else:
             go()

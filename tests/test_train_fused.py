@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import knobs, load_golden
+from gsvc_amd.knobs import Knob
 
 pytestmark = pytest.mark.gpu
 
@@ -29,8 +30,8 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(params=["band", "wg256"])
 def tile_kernel(request, cuda):
     """The fused step's tile kernel: two 8-row band waves per tile (production)
-    or the 256-thread workgroup per tile (gsvc_debug_set(8, 1), A/B)."""
-    with knobs((8, 1 if request.param == "wg256" else 0)):
+    or the 256-thread workgroup per tile (Knob.TILE_WG256 = 1, A/B)."""
+    with knobs((Knob.TILE_WG256, 1 if request.param == "wg256" else 0)):
         yield request.param
 
 

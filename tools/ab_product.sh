@@ -22,7 +22,7 @@ for rep in $(seq 1 $REPS); do
     if [ "$d" = cur ]; then v=cur; src=$OUT/cur.so; else v=$(basename "$d"); src=$d/libgsvc_amd.so; fi
     [ -f "$src" ] || continue
     cp "$src" $LIB
-    timeout -k 10 300 python -u bench.py --full --no-cpu ${AB_SECONDARY:---no-secondary} "$@" > "$OUT/${v}_$rep.log" 2>&1 \
+    timeout -k 10 300 python -u bench.py --full --no-cpu ${AB_SECONDARY---no-secondary} "$@" > "$OUT/${v}_$rep.log" 2>&1 \
       || { echo "variant $v failed"; tail -5 "$OUT/${v}_$rep.log"; cp $OUT/cur.so $LIB; exit 1; }
     python3 - "$OUT/${v}_$rep.log" "$v" <<'PY'
 import json, sys

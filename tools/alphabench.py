@@ -57,7 +57,7 @@ def main():
     ap.add_argument("--splats", type=int, nargs="+", default=[10000, 50000])
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--knob", action="append", default=[],
-                    help="K=V: gsvc_debug_set(K, V) first (A/B; knob 9 = 1: shuffle reductions)")
+                    help="K=V: gsvc_debug_set(K, V) first (A/B; K a number of gsvc_amd.knobs.Knob, e.g. 30=1: the backward without per-entry sums, wrong results)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.knob:

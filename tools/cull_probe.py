@@ -39,6 +39,7 @@ def blocks_hit(x, y, a, b, c, bx0, by0, px, py):
 
 def main():
     from conftest import knobs
+    from gsvc_amd.knobs import Knob
     from gsvc_amd import ops
     from gsvc_amd.render import render_frame_sum
     dev = torch.device("cuda:0")
@@ -50,7 +51,7 @@ def main():
     bg = torch.ones(3, device=dev)
     with torch.no_grad():
         sparse = render_frame_sum(xyz, chol, feat, H, W, bg, cholesky_bound=bound)
-        with knobs((0, 2)):
+        with knobs((Knob.FWD_MODE, 2)):
             banded = render_frame_sum(xyz, chol, feat, H, W, bg, cholesky_bound=bound)
         tb = ((W + 15) // 16, (H + 15) // 16, 1)
         xys, depths, radii, conics, nth = ops.project_gaussians_2d_forward(

@@ -2,7 +2,7 @@
 
     python tools/fbench.py [--splats 10000 50000] [--iters 200] [--chol-scale 1]
 
-For each rasterizer mode (gsvc_debug_set(0)) and each extra knob pass, times
+For each rasterizer mode (Knob.FWD_MODE) and each extra knob pass, times
 ``iters`` back-to-back frame renders (plain library calls; the slab entries
 refuse graph capture since round 5) and prints microseconds per frame, best
 of three.  Every pass's image must equal the first one bit for bit.
@@ -24,6 +24,7 @@ os.environ.setdefault("GSVC_DIAG", "1")
 import torch  # noqa: E402
 
 from gsvc_amd import _lib as L  # noqa: E402
+from gsvc_amd.knobs import Knob  # noqa: E402
 
 H, W = 1080, 1920
 
@@ -39,7 +40,7 @@ def main():
                     help="render the bench's frame model after this many training iterations "
                          "(trained density) instead of random splats")
     ap.add_argument("--modes", type=int, nargs="+", default=[0],
-                    help="rasterizer modes (gsvc_debug_set(0)); 0 = automatic")
+                    help="rasterizer modes (Knob.FWD_MODE); 0 = automatic")
     ap.add_argument("--knob", type=int, nargs=2, action="append", default=[],
                     metavar=("KEY", "VALUE"), help="extra gsvc_debug_set for a second pass")
     ap.add_argument("--set", type=int, nargs=2, action="append", default=[],
@@ -50,10 +51,10 @@ def main():
     ap.add_argument("--stamps-out", default=None,
                     help="with --stamps: save the raw per-tile stamps (us) and entry counts (npz)")
     ap.add_argument("--id-stamps", default=None, const="-", nargs="?",
-                    help="stamp the production id-slab composite (knob 39) and print its phases "
+                    help="stamp the production id-slab composite (Knob.RENDER_STAMPS) and print its phases "
                          "by entry count; optional npz path for the raw stamps")
     ap.add_argument("--proj-stamps", action="store_true",
-                    help="also stamp the projection kernel's waves (knob 5) and print phases")
+                    help="also stamp the projection kernel's waves (Knob.STAMP) and print phases")
     args = ap.parse_args()
     args.iters = max(2, args.iters - args.iters % 2)
     lib = L.load()
@@ -98,10 +99,10 @@ def main():
             # every pass from a zeroed workspace: the captured graph below freezes
             # each frame's parity (see the module docstring), so the counts it
             # leaves are stale, and a variant that reads the slab memory in
-            # another layout (knob 24: ids) must not inherit them
+            # another layout (Knob.RECORD_SLABS: records) must not inherit them
             torch.cuda.synchronize()
             ws.zero_()
-            lib.gsvc_debug_set(0, mode)
+            lib.gsvc_debug_set(Knob.FWD_MODE, mode)
             if kv:
                 if lib.gsvc_debug_set(kv[0], kv[1]) < 0:
                     raise ValueError("unknown A/B knob key (gsvc_debug_set returned -1)")
@@ -152,11 +153,11 @@ def main():
             ntiles = ((W + 15) // 16) * ((H + 15) // 16)
             st = torch.zeros((ntiles, 4), dtype=torch.int64, device=dev)
             lib.gsvc_debug_set_ptr(ctypes.c_void_p(st.data_ptr()))
-            lib.gsvc_debug_set(0, 7)
+            lib.gsvc_debug_set(Knob.FWD_MODE, 7)
             for _ in range(5):
                 frame()
             torch.cuda.synchronize()
-            lib.gsvc_debug_set(0, 0)
+            lib.gsvc_debug_set(Knob.FWD_MODE, 0)
             lib.gsvc_debug_set_ptr(None)
             t = st.cpu().numpy().astype(np.float64) * 0.01  # 100 MHz ticks -> us
             t0 = t[:, 0].min()
@@ -183,11 +184,11 @@ def main():
             ntiles = ((W + 15) // 16) * ((H + 15) // 16)
             st = torch.zeros((ntiles, 8), dtype=torch.int64, device=dev)
             lib.gsvc_debug_set_ptr(ctypes.c_void_p(st.data_ptr()))
-            lib.gsvc_debug_set(39, 1)
+            lib.gsvc_debug_set(Knob.RENDER_STAMPS, 1)
             for _ in range(5):
                 frame()
             torch.cuda.synchronize()
-            lib.gsvc_debug_set(39, 0)
+            lib.gsvc_debug_set(Knob.RENDER_STAMPS, 0)
             lib.gsvc_debug_set_ptr(None)
             raw = st.cpu().numpy()
             cnt = raw[:, 5].copy()
@@ -215,11 +216,11 @@ def main():
             waves = (n + 63) // 64
             st = torch.zeros((waves + 8, 4), dtype=torch.int64, device=dev)
             lib.gsvc_debug_set_ptr(ctypes.c_void_p(st.data_ptr()))
-            lib.gsvc_debug_set(5, 1)
+            lib.gsvc_debug_set(Knob.STAMP, 1)
             for _ in range(5):
                 frame()
             torch.cuda.synchronize()
-            lib.gsvc_debug_set(5, 0)
+            lib.gsvc_debug_set(Knob.STAMP, 0)
             lib.gsvc_debug_set_ptr(None)
             t = st[:waves].cpu().numpy().astype(np.float64) * 0.01
             t0 = t[:, 0].min()
@@ -228,7 +229,7 @@ def main():
                                   start=q(t[:, 0] - t0), project=q(t[:, 1] - t[:, 0]),
                                   insert=q(t[:, 2] - t[:, 1]), reduce=q(t[:, 3] - t[:, 2]),
                                   end=q(t[:, 3] - t0))), flush=True)
-    lib.gsvc_debug_set(0, 0)
+    lib.gsvc_debug_set(Knob.FWD_MODE, 0)
 
 
 if __name__ == "__main__":

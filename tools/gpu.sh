@@ -14,13 +14,13 @@
 #                                      the trained composite and training tile kernel
 #   pmc_sq TAG                         SQ busy / wait / LDS-conflict cycles of the same
 #   pmc_final TAG                      both, for train50k and render10k -> pmc_valu.json
-#   ablate TAG "bits" [tbench args]    training tile kernel diagnostic bits (knob 13)
+#   ablate TAG "bits" [tbench args]    training tile kernel diagnostic bits (knob 13, TILE_ABLATE)
 #                                      on frozen trained-density steps
 #   fbench_ab TAG [fbench args]        composite A/B by fbench + kernel trace
 #   shared_ranks TAG                   N = 1, 2, 4 bench ranks sharing one GPU (gloo)
 #   final TAG                          bench.py --full + rocprofv3 kernel trace of the bench
-#   alpha_ab TAG [KNOB ['V1 V2']]      alpha path A/B (default knob 9: backward DPP vs shuffle sums;
-#                                      knob 18 = 100000: forward without lane-group lists),
+#   alpha_ab TAG KNOB ['V1 V2']        alpha path A/B of one live knob (gsvc_amd/knobs.py; e.g. 30
+#                                      'V1 V2' = '0 1': the backward without its per-entry sums),
 #                                      interleaved twice
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -134,7 +134,7 @@ final)
   run bench 900 python bench.py --full
   run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o b --output-format csv -- python3 bench.py --full --no-cpu ;;
 alpha_ab)
-  KN=${1:-9}; VALS=${2:-"0 1"}
+  KN=${1:?knob number (gsvc_amd/knobs.py)}; VALS=${2:-"0 1"}
   for rep in 1 2; do
     for k in $VALS; do
       run "k${k}_$rep" 200 rocprofv3 --kernel-trace --stats -d "$OUT/k${k}_$rep" -o a --output-format csv -- python3 tools/alphabench.py --splats 50000 --calls 100 --knob $KN=$k

@@ -24,6 +24,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=2)
     a = ap.parse_args()
     from conftest import knobs
+    from gsvc_amd.knobs import Knob
     from gsplat.project_gaussians_2d import project_gaussians_2d
     from gsplat.rasterize_sum import rasterize_gaussians_sum
     dev = torch.device("cuda:0")
@@ -43,7 +44,7 @@ def main():
 
     for r in range(a.repeat):
         fast, nth = fwd()
-        with knobs((0, 1), *[tuple(k) for k in a.knob]):
+        with knobs((Knob.FWD_MODE, 1), *[tuple(k) for k in a.knob]):
             ref, _ = fwd()
         torch.cuda.synchronize()
         bad = (fast != ref).any(-1)

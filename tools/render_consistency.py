@@ -29,6 +29,7 @@ def main():
     else:
         z = np.load(sys.argv[1])
     from conftest import knobs
+    from gsvc_amd.knobs import Knob
     from gsvc_amd.frame import make_frame_model
     from tile_counts import tile_counts
     dev = torch.device("cuda:0")
@@ -51,10 +52,10 @@ def main():
         outs["fused_first"] = m()["render"].clone()
         from gsvc_amd.render import render_frame_sum
         bound = torch.tensor([0.5, 0.0, 0.5], device=dev)
-        with knobs((0, 2)):  # the banded kernel over record slabs
+        with knobs((Knob.FWD_MODE, 2)):  # the banded kernel over record slabs
             outs["banded_records"] = render_frame_sum(m._xyz, m._cholesky, m._features_dc, H, W,
                                                       m.background, cholesky_bound=bound).clone()
-        with knobs((24, 1)):  # records at the automatic mode
+        with knobs((Knob.RECORD_SLABS, 1)):  # records at the automatic mode
             outs["records"] = render_frame_sum(m._xyz, m._cholesky, m._features_dc, H, W,
                                                m.background, cholesky_bound=bound).clone()
         for _ in range(30):
@@ -63,7 +64,7 @@ def main():
         m2 = model(False)
         outs["op_path"] = m2()["render"].clone()
         outs["op_path_2"] = m2()["render"].clone()
-        with knobs((0, 1)):
+        with knobs((Knob.FWD_MODE, 1)):
             outs["python_fn"] = m2()["render"].clone()
         from gsvc_amd import ops
         xys, _, radii, _, _ = ops.project_gaussians_2d_forward(

@@ -30,9 +30,10 @@ def main():
     ap.add_argument("--stamps", action="store_true",
                     help="also stamp the fused step's tile kernel and print phases")
     ap.add_argument("--tile-kernel", choices=["band", "wg256"], default="band",
-                    help="two 8-row bands per tile (production) or the 256-thread kernel (knob 8 = 1)")
+                    help="two 8-row bands per tile (production) or the 256-thread kernel (Knob.TILE_WG256; "
+                         "diagnostic library only)")
     ap.add_argument("--knob", action="append", default=[],
-                    help="A/B knob K=V (gsvc_debug_set), repeatable")
+                    help="A/B knob K=V (gsvc_debug_set; K a number of gsvc_amd.knobs.Knob), repeatable")
     ap.add_argument("--knob-after", action="append", default=[],
                     help="knob K=V set only after the warmup (diagnostic variants that change "
                          "results must not steer the training state being measured)")
@@ -66,11 +67,15 @@ def main():
     from gsvc_amd.frame import make_frame_model, synthetic_gt
     from gsvc_amd import _lib
     from gsvc_amd import train as _train
+    from gsvc_amd.knobs import Knob
     if a.order_every is not None:
         _train.ORDER_REFRESH_EVERY = a.order_every
     if a.rebuild_every is not None:
         _train.CARRY_REBUILD_EVERY = a.rebuild_every
-    _lib.load().gsvc_debug_set(8, 1 if a.tile_kernel == "wg256" else 0)
+    if a.tile_kernel == "wg256":  # (the product library, GSVC_DIAG=0, has no knobs)
+        if _lib.product_active():
+            raise SystemExit("--tile-kernel wg256 needs the diagnostic library (GSVC_DIAG=1)")
+        _lib.load().gsvc_debug_set(Knob.TILE_WG256, 1)
     for kv in a.knob:
         k, v = kv.split("=")
         if _lib.load().gsvc_debug_set(int(k), int(v)) < 0:
@@ -173,10 +178,10 @@ def main():
         lib = L.load()
         st = torch.zeros(((a.splats + 63) // 64 + 4096, 8), dtype=torch.int64, device=dev)  # waves of any per-workgroup split
         lib.gsvc_debug_set_ptr(ctypes.c_void_p(st.data_ptr()))
-        lib.gsvc_debug_set(5, 1)
+        lib.gsvc_debug_set(Knob.STAMP, 1)
         model.train_iter(gt, a.warmup + a.iters + 300)
         torch.cuda.synchronize()
-        lib.gsvc_debug_set(5, 0)
+        lib.gsvc_debug_set(Knob.STAMP, 0)
         lib.gsvc_debug_set_ptr(None)
         t = st.cpu().numpy().astype(np.float64) * 0.01
         t = t[t[:, 3] > 0]
@@ -198,10 +203,10 @@ def main():
         lib = L.load()
         st = torch.zeros(((a.splats + 255) // 256 * 4 + 8, 8), dtype=torch.int64, device=dev)
         lib.gsvc_debug_set_ptr(ctypes.c_void_p(st.data_ptr()))
-        lib.gsvc_debug_set(5, 4)
+        lib.gsvc_debug_set(Knob.STAMP, 4)
         model.train_iter(gt, a.warmup + a.iters + 400)
         torch.cuda.synchronize()
-        lib.gsvc_debug_set(5, 0)
+        lib.gsvc_debug_set(Knob.STAMP, 0)
         lib.gsvc_debug_set_ptr(None)
         t = st.cpu().numpy().astype(np.float64) * 0.01
         loss_wg = t[:4]
@@ -223,10 +228,10 @@ def main():
         ntiles = ((W + 15) // 16) * ((H + 15) // 16)
         st = torch.zeros((ntiles, 8), dtype=torch.int64, device=dev)
         lib.gsvc_debug_set_ptr(ctypes.c_void_p(st.data_ptr()))
-        lib.gsvc_debug_set(5, 2 if a.tile_kernel == "wg256" else 3)
+        lib.gsvc_debug_set(Knob.STAMP, 2 if a.tile_kernel == "wg256" else 3)
         model.train_iter(gt, a.warmup + a.iters + 1)
         torch.cuda.synchronize()
-        lib.gsvc_debug_set(5, 0)
+        lib.gsvc_debug_set(Knob.STAMP, 0)
         lib.gsvc_debug_set_ptr(None)
         t = st.cpu().numpy().astype(np.float64) * 0.01
         if a.stamps_out:

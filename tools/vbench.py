@@ -1,7 +1,7 @@
 """Batched (GOP) render throughput, bench.py's video_decode, with an optional
 A/B pass of gsvc_debug_set(KEY, VALUE).
 
-    python tools/vbench.py [--frames 8] [--knob 2 8]
+    python tools/vbench.py [--frames 8] [--knob 25 1]
 """
 import argparse
 import json
