@@ -8,9 +8,13 @@ re-exports this module so GSVC's ``from gsplat.project_gaussians_2d import
 project_gaussians_2d`` / ``from gsplat.rasterize_sum import
 rasterize_gaussians_sum`` run unchanged on ROCm.
 
+The compression stage -- quantized frame models, the packed stream and its
+decoder -- is ``gsvc_amd.compress`` / ``gsvc_amd.quantize``.
+
 Out of scope (3DGS and unused 2D variants): ``project_gaussians``,
 ``project_gaussians_2d_scale_rot``, ``spherical_harmonics`` and the C != 3
-``nd_*`` rasterizers; they are importable and raise NotImplementedError.
+``nd_*`` rasterizers; they are importable and raise NotImplementedError
+(DESIGN.md §10).
 """
 from __future__ import annotations
 
@@ -36,7 +40,7 @@ def _out_of_scope(name):
     def fn(*args, **kwargs):
         raise NotImplementedError(
             f"{name} belongs to the 3DGS / unused parts of gsplat and is out of scope for "
-            "gsvc_amd (DESIGN.md §7)")
+            "gsvc_amd (DESIGN.md §10)")
     fn.__name__ = name
     return fn
 

@@ -115,6 +115,11 @@ _SIGS = {
                                _P, _P, _P, _P],
     "gsvc_rasterize_backward": [_U, _U, _U, _U, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                 _P, _P],
+    "gsvc_quant_workspace_bytes": [_I],
+    "gsvc_quant_params_forward": [_I] + [_P] * 16 + [_P, _SZ, _P],
+    "gsvc_quant_params_backward": [_I] + [_P] * 15 + [_P, _SZ, _P],
+    "gsvc_pack_splats": [_I, _P, _P, _P, _P, _P],
+    "gsvc_unpack_splats": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _LL, _P],
 }
 # include/gsvc_amd_diag.h: the diagnostic library's extra entry points
 _DIAG_SIGS = {
@@ -142,6 +147,7 @@ _RESTYPE = {
     "gsvc_render_frames_zeroed_bytes": _SZ,
     "gsvc_ssim_workspace_bytes": _SZ,
     "gsvc_ssim_backward_scratch_bytes": _SZ,
+    "gsvc_quant_workspace_bytes": _SZ,
 }
 
 ABI_VERSION = 2

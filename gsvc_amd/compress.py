@@ -1,0 +1,462 @@
+"""Compression stage: quantized frame models, the packed stream, its decoder.
+
+``GaussianVideoFrameQ`` / ``GaussianVideoDelta`` mirror ``GaussianVideo_frame``
+/ ``GaussianVideo_delta`` of the reference's GaussianSplats_Compress.py:11-193:
+the same parameters and buffers, ``forward``, ``forward_quantize``,
+``train_iter_quantize`` and ``_init_data``.  An overfit frame model is
+fine-tuned under quantization -- positions through fp16, Cholesky entries
+through a learned 6-bit uniform quantizer, colours through a 2-stage residual
+VQ -- and a non-key frame is a delta on the previous frame's parameters.  The
+quantization itself is one kernel each way (``quantize.quantize_params``); the
+render and its backward are the existing operators, the optimizer the existing
+``Adan``.
+
+``encode_frame`` writes a model as the fixed-length stream of
+include/gsvc_amd.h (256-byte header + 7 bytes per splat), ``decode_frames``
+turns a list of such streams into images with one unpack launch and
+``render_frames_sum``; ``compress_video`` is the loop of
+train_video_Compress.py:240-271 without its image and video writing.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes
+import math
+import struct
+from collections import namedtuple
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib as L
+from .adan import Adan
+from .frame import loss_fn
+from .project_gaussians_2d import project_gaussians_2d
+from .quantize import (FakeQuantizationHalf, ResidualVQ8, UniformQuantizer, fixed_bits,
+                       quantize_params, vq_loss_from_sums, zeroth_order_bits, _table_bits)
+from .rasterize_sum import rasterize_gaussians_sum
+from .render import render_frame_sum, render_frames_sum
+
+STREAM_MAGIC = 0x51565347  # "GSVQ"
+STREAM_VERSION = 1
+HEADER_BYTES = 256
+SPLAT_BYTES = 7
+_HEADER = struct.Struct("<IIiIII3f3f48f")  # magic, version, N, H, W, flags, scale, beta, codebooks
+FLAG_DELTA = 1
+
+# unit_bit entry of one parameter group: the bits the packed stream writes, and
+# an estimate of what an entropy coder would (None in training mode)
+Bits = namedtuple("Bits", ["fixed", "entropy_estimate"])
+
+
+class _QuantFrame(nn.Module):
+    """What the key-frame and delta models share."""
+    _delta = False
+
+    def __init__(self, loss_type="L2", **kwargs):
+        super().__init__()
+        self.loss_type = loss_type
+        self.init_num_points = n = kwargs["num_points"]
+        self.H, self.W = kwargs["H"], kwargs["W"]
+        self.BLOCK_W, self.BLOCK_H = kwargs["BLOCK_W"], kwargs["BLOCK_H"]
+        self.tile_bounds = ((self.W + self.BLOCK_W - 1) // self.BLOCK_W,
+                            (self.H + self.BLOCK_H - 1) // self.BLOCK_H, 1)
+        self.device = kwargs["device"]
+        self._xyz = nn.Parameter(torch.atanh(2 * (torch.rand(n, 2) - 0.5)))
+        self._cholesky = nn.Parameter(torch.rand(n, 3))
+        self._features_dc = nn.Parameter(torch.rand(n, 3))
+        self.last_size = (self.H, self.W)
+        if self._delta:
+            self.register_buffer("p_xyz", torch.atanh(2 * (torch.rand(n, 2) - 0.5)))
+            self.register_buffer("p_cholesky", torch.rand(n, 3))
+            self.register_buffer("p_features_dc", torch.rand(n, 3))
+        self.register_buffer("_opacity", torch.ones((n, 1)))
+        self.register_buffer("background", torch.ones(3))
+        self.register_buffer("bound", torch.tensor([0.5, 0.5]).view(1, 2))
+        self.register_buffer("cholesky_bound", torch.tensor([0.5, 0, 0.5]).view(1, 3))
+        self.quantize = kwargs["quantize"]
+        if self.quantize:
+            self.xyz_quantizer = FakeQuantizationHalf.apply
+            self.features_dc_quantizer = ResidualVQ8(kmeans_iters=5)
+            self.cholesky_quantizer = UniformQuantizer(signed=False, bits=6, learned=True,
+                                                       num_channels=3)
+        if kwargs.get("opt_type", "adan") == "adam":
+            self.optimizer = torch.optim.Adam(self.parameters(), lr=kwargs["lr"])
+        else:
+            self.optimizer = Adan(self.parameters(), lr=kwargs["lr"])
+        self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=20000, gamma=0.5)
+
+    def _init_data(self):
+        self.cholesky_quantizer._init_data(self._cholesky)
+
+    def _prev(self):
+        return (self.p_xyz, self.p_cholesky, self.p_features_dc) if self._delta else None
+
+    @property
+    def get_xyz(self):
+        return torch.tanh(self._xyz + self.p_xyz) if self._delta else torch.tanh(self._xyz)
+
+    @property
+    def get_features(self):
+        return self._features_dc + self.p_features_dc if self._delta else self._features_dc
+
+    @property
+    def get_cholesky_elements(self):
+        if self._delta:
+            return self._cholesky + self.p_cholesky + self.cholesky_bound
+        return self._cholesky + self.cholesky_bound
+
+    def _render(self, means, cholesky_elements, colors):
+        self.xys, depths, self.radii, conics, num_tiles_hit = project_gaussians_2d(
+            means, cholesky_elements, self.H, self.W, self.tile_bounds)
+        out_img = rasterize_gaussians_sum(self.xys, depths, self.radii, conics, num_tiles_hit,
+                                          colors, self._opacity, self.H, self.W, self.BLOCK_H,
+                                          self.BLOCK_W, background=self.background,
+                                          return_alpha=False)
+        out_img = torch.clamp(out_img, 0, 1)
+        return out_img.view(-1, self.H, self.W, 3).permute(0, 3, 1, 2).contiguous()
+
+    def forward(self):
+        """The unquantized render (GaussianSplats_Compress.py:62-69, 157-163)."""
+        return {"render": self._render(self.get_xyz, self.get_cholesky_elements, self.get_features)}
+
+    def quantized(self, commit=None):
+        """quantize_params of this model: (xq, Lq, cq, codes_chol, codes_rgb,
+        commit_sums); initialises the codebooks on first use.  The commitment
+        sums are computed in training mode or with autograd on (``commit``
+        overrides); otherwise they are None."""
+        if commit is None:
+            commit = self.training or torch.is_grad_enabled()
+        if not self.quantize:
+            raise RuntimeError("the model was built with quantize=False")
+        vq = self.features_dc_quantizer
+        if not vq.is_initted():
+            vq.init_codebooks(self._features_dc)
+        uq = self.cholesky_quantizer
+        return quantize_params(self._xyz, self._cholesky, self._features_dc, uq.scale, uq.beta,
+                               vq.codebooks, self.cholesky_bound, self._prev(), commit)
+
+    def forward_quantize(self):
+        """GaussianSplats_Compress.py:71-84, 165-179.  ``unit_bit`` lists, for
+        positions, Cholesky codes, (unused) and colours, a ``Bits(fixed,
+        entropy_estimate)``: the bits ``encode_frame`` writes for the group
+        (header fields included: they sum to 8 * len(encode_frame(self))), and
+        in eval mode the zeroth-order entropy of the codes plus the table cost
+        quantize.py:72-80 counts -- an estimate; the reference's figure comes
+        from an ANS coder."""
+        n = self._xyz.shape[0]
+        vq = self.features_dc_quantizer
+        xq, Lq, cq, codes_chol, codes_rgb, sums = self.quantized()
+        if self.training:
+            vq.ema_update(self._features_dc, codes_rgb)
+        # inference (eval mode, no autograd) skips the commitment sums: the loss is 0 there
+        vq_loss = (xq.new_zeros(()) if sums is None
+                   else vq_loss_from_sums(sums, n, vq.commitment_weight))
+        if (not torch.is_grad_enabled() and xq.is_cuda and self.BLOCK_H == 16 and self.BLOCK_W == 16):
+            # inference: the one-call frame render applies tanh itself
+            out_img = render_frame_sum(xq, Lq, cq, self.H, self.W, self.background, xyz_tanh=True,
+                                       cholesky_bound=None)
+        else:
+            out_img = self._render(torch.tanh(xq), Lq, cq)
+        m_fix, s_fix, c_fix = fixed_bits(n)
+        tables = 6 * 32, vq.codebooks.numel() * 32
+        misc = 8 * HEADER_BYTES - sum(tables)
+        est = [None] * 4
+        if not self.training:
+            hs, us = zeroth_order_bits(codes_chol.cpu().numpy())
+            hc, uc = zeroth_order_bits(codes_rgb.cpu().numpy())
+            est = [m_fix, hs + _table_bits(us) + tables[0], 0, hc + _table_bits(uc) + tables[1]]
+        unit_bit = [Bits(m_fix + misc, est[0]), Bits(s_fix + tables[0], est[1]), Bits(0, est[2]),
+                    Bits(c_fix + tables[1], est[3])]
+        return {"render": out_img, "vq_loss": vq_loss, "unit_bit": unit_bit}
+
+    def train_iter_quantize(self, gt_image):
+        """GaussianSplats_Compress.py:86-98, 181-193."""
+        render_pkg = self.forward_quantize()
+        image = render_pkg["render"]
+        loss = loss_fn(image.squeeze(0), gt_image.squeeze(0), self.loss_type,
+                       lambda_value=0) + render_pkg["vq_loss"]
+        loss.backward()
+        with torch.no_grad():
+            mse_loss = F.mse_loss(image, gt_image)
+            psnr = 10 * math.log10(1.0 / mse_loss.item())
+        self.optimizer.step()
+        self.optimizer.zero_grad(set_to_none=True)
+        self.scheduler.step()
+        return loss, psnr
+
+
+class GaussianVideoFrameQ(_QuantFrame):
+    """A key frame under quantization (GaussianVideo_frame)."""
+    _delta = False
+
+
+class GaussianVideoDelta(_QuantFrame):
+    """A non-key frame: quantized deltas on the buffers ``p_xyz``, ``p_cholesky``,
+    ``p_features_dc`` (GaussianVideo_delta)."""
+    _delta = True
+
+
+# --------------------------------------------------------------------------
+# the packed stream
+
+def _header(n, H, W, delta, scale, beta, codebooks) -> bytes:
+    vals = [float(v) for v in scale] + [float(v) for v in beta] + [float(v) for v in codebooks]
+    h = _HEADER.pack(STREAM_MAGIC, STREAM_VERSION, n, H, W, FLAG_DELTA if delta else 0, *vals)
+    return h + bytes(HEADER_BYTES - len(h))
+
+
+def parse_header(buf) -> dict:
+    """Fields of one frame stream's header; raises ValueError on a wrong magic,
+    version, length or N."""
+    if len(buf) < HEADER_BYTES:
+        raise ValueError(f"stream truncated: {len(buf)} bytes, the header is {HEADER_BYTES}")
+    f = _HEADER.unpack_from(buf, 0)
+    if f[0] != STREAM_MAGIC:
+        raise ValueError(f"wrong magic 0x{f[0]:08x}")
+    if f[1] != STREAM_VERSION:
+        raise ValueError(f"stream version {f[1]}, not {STREAM_VERSION}")
+    n = f[2]
+    if n < 0 or len(buf) != HEADER_BYTES + SPLAT_BYTES * n:
+        raise ValueError(f"stream of {len(buf)} bytes does not hold N = {n} splats")
+    return dict(N=n, H=f[3], W=f[4], delta=bool(f[5] & FLAG_DELTA),
+                scale=np.array(f[6:9], np.float32), beta=np.array(f[9:12], np.float32),
+                codebooks=np.array(f[12:60], np.float32).reshape(2, 8, 3))
+
+
+def pack_planes_host(xyz, codes_chol, codes_rgb) -> bytes:
+    """The two planes (7 N bytes) from positions and codes, on the host."""
+    n = xyz.shape[0]
+    a = np.ascontiguousarray(np.asarray(xyz, np.float32).astype("<f2")).tobytes()
+    cc = np.asarray(codes_chol).astype(np.uint32) & 63
+    cr = np.asarray(codes_rgb).astype(np.uint32) & 7
+    w = cc[:, 0] | cc[:, 1] << 6 | cc[:, 2] << 12 | cr[:, 0] << 18 | cr[:, 1] << 21
+    b = np.stack([w & 0xff, (w >> 8) & 0xff, (w >> 16) & 0xff], axis=1).astype(np.uint8)
+    return a + b.reshape(n * 3).tobytes()
+
+
+def encode_frame(model) -> bytes:
+    """The model's quantized parameters as one frame stream:
+    ``256 + 7 * N`` bytes."""
+    with torch.no_grad():
+        _, _, _, codes_chol, codes_rgb, _ = model.quantized(commit=False)
+        xyz = model._xyz.detach().float().contiguous()
+        n = xyz.shape[0]
+        uq, vq = model.cholesky_quantizer, model.features_dc_quantizer
+        head = _header(n, model.H, model.W, model._delta, uq.scale.detach().cpu().tolist(),
+                       uq.beta.detach().cpu().tolist(), vq.codebooks.cpu().reshape(-1).tolist())
+        if xyz.is_cuda:
+            planes = torch.empty((SPLAT_BYTES * n,), dtype=torch.uint8, device=xyz.device)
+            L.call("gsvc_pack_splats", n, L.ptr(xyz), L.ptr(codes_chol), L.ptr(codes_rgb),
+                   L.ptr(planes), L.stream(xyz.device))
+            body = planes.cpu().numpy().tobytes()
+        else:
+            body = pack_planes_host(xyz.numpy(), codes_chol.numpy(), codes_rgb.numpy())
+    return head + body
+
+
+def unpack_frames_host(streams: Sequence[bytes], cholesky_bound=(0.5, 0.0, 0.5), prev=None):
+    """The decoder's arithmetic in numpy: per frame (xq, Lq, cq, Lpre), fp32,
+    one rounding per op as in csrc/quant.hip.  ``prev`` = (xq, Lpre, cq) of the
+    frame before the first one, for a stream that starts with a delta frame."""
+    bound = np.asarray(cholesky_bound, np.float32).reshape(1, 3)
+    out = []
+    for k, buf in enumerate(streams):
+        h = parse_header(buf)
+        n = h["N"]
+        a = np.frombuffer(buf, "<f2", count=2 * n, offset=HEADER_BYTES).reshape(n, 2)
+        b = np.frombuffer(buf, np.uint8, count=3 * n, offset=HEADER_BYTES + 4 * n).reshape(n, 3)
+        w = b[:, 0].astype(np.uint32) | b[:, 1].astype(np.uint32) << 8 | b[:, 2].astype(np.uint32) << 16
+        codes = np.stack([w & 63, (w >> 6) & 63, (w >> 12) & 63], axis=1).astype(np.float32)
+        i0, i1 = ((w >> 18) & 7).astype(np.int64), ((w >> 21) & 7).astype(np.int64)
+        xq = a.astype(np.float32)
+        deq = codes * h["scale"][None] + h["beta"][None]
+        Lq, Lpre = deq + bound, deq
+        cq = h["codebooks"][0][i0] + h["codebooks"][1][i1]
+        if h["delta"]:
+            if prev is None:
+                raise ValueError(f"delta frame {k} has no predecessor")
+            if n > prev[0].shape[0]:
+                raise ValueError(f"delta frame {k} has {n} splats, its predecessor {prev[0].shape[0]}")
+            xq, Lq, Lpre, cq = xq + prev[0][:n], Lq + prev[1][:n], Lpre + prev[1][:n], cq + prev[2][:n]
+        out.append((xq, Lq, cq, Lpre))
+        prev = (xq, Lpre, cq)
+    return out
+
+
+def unpack_frames(streams: Sequence[bytes], device, cholesky_bound=None, prev=None):
+    """One gsvc_unpack_splats launch for the concatenated frame streams:
+    ``(xq, Lq, cq, Lpre, sizes, (H, W))`` with the frames' splats concatenated.
+    ``prev`` = (xq, Lpre, cq) of the frame before the first (device tensors)."""
+    device = torch.device(device)
+    blob = b"".join(streams)
+    offs = [0]
+    for s in streams:
+        offs.append(offs[-1] + len(s))
+    # every header is checked here before anything is sized by it (ValueError);
+    # the entry checks them again, and what spans frames, before it launches
+    heads = [parse_header(s) for s in streams]
+    sizes = [h["N"] for h in heads]
+    hw = (heads[0]["H"], heads[0]["W"]) if heads else (0, 0)
+    total = sum(sizes)
+    if cholesky_bound is None:
+        cholesky_bound = torch.tensor([0.5, 0.0, 0.5], device=device)
+    bound = cholesky_bound.detach().to(device=device, dtype=torch.float32).contiguous()
+    dev_stream = torch.frombuffer(bytearray(blob or b"\0"), dtype=torch.uint8).to(device)
+    xq = torch.empty((total, 2), dtype=torch.float32, device=device)
+    Lq, cq, Lpre = (torch.empty((total, 3), dtype=torch.float32, device=device) for _ in range(3))
+    offs_c = (ctypes.c_longlong * len(offs))(*offs)
+    p = [None, None, None]
+    prev_n = 0
+    if prev is not None:
+        p = [t.detach().to(device=device, dtype=torch.float32).contiguous() for t in prev]
+        prev_n = p[0].shape[0]
+    L.call("gsvc_unpack_splats", len(streams), ctypes.c_char_p(blob), offs_c, L.ptr(dev_stream),
+           L.ptr(bound), L.ptr(p[0]), L.ptr(p[1]), L.ptr(p[2]), prev_n, L.ptr(xq), L.ptr(Lq),
+           L.ptr(cq), L.ptr(Lpre), total, L.stream(device))
+    return xq, Lq, cq, Lpre, sizes, (int(hw[0]), int(hw[1]))
+
+
+def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: bool = False):
+    """Frame streams (``encode_frame``) to images [F, 3, H, W].
+
+    On a HIP device: one unpack launch for all frames, then
+    ``render_frames_sum``.  A delta frame adds the DECODED parameters of the
+    frame before it; ``prev`` carries them from an earlier call
+    (``return_state=True`` also returns (xq, Lpre, cq) of the last frame).
+    CPU: the numpy decoder and the CPU operators, frame by frame."""
+    device = torch.device(device)
+    if len(streams) == 0:
+        raise ValueError("decode_frames: no frames")
+    if device.type == "cuda":
+        xq, Lq, cq, Lpre, sizes, (H, W) = unpack_frames(streams, device, prev=prev)
+        bg = torch.ones(3, device=device)
+        imgs = render_frames_sum(xq, Lq, cq, sizes, H, W, bg, xyz_tanh=True, cholesky_bound=None)
+        last = sum(sizes[:-1])
+        state = (xq[last:], Lpre[last:], cq[last:])
+    else:
+        p = None if prev is None else tuple(np.asarray(t.detach().cpu().numpy(), np.float32) for t in prev)
+        frames = unpack_frames_host(streams, prev=p)
+        h0 = parse_header(streams[0])
+        H, W = h0["H"], h0["W"]
+        tb = ((W + 15) // 16, (H + 15) // 16, 1)
+        imgs = []
+        for xq, Lq, cq, _ in frames:
+            n = xq.shape[0]
+            xys, depths, radii, conics, nth = project_gaussians_2d(
+                torch.tanh(torch.from_numpy(xq)), torch.from_numpy(Lq), H, W, tb)
+            img = rasterize_gaussians_sum(xys, depths, radii, conics, nth, torch.from_numpy(cq),
+                                          torch.ones(n, 1), H, W, 16, 16, background=torch.ones(3),
+                                          return_alpha=False)
+            imgs.append(torch.clamp(img, 0, 1).view(H, W, 3).permute(2, 0, 1))
+        imgs = torch.stack(imgs).contiguous()
+        xq, _, cq, Lpre = frames[-1]
+        state = tuple(torch.from_numpy(np.ascontiguousarray(t)) for t in (xq, Lpre, cq))
+    return (imgs, state) if return_state else imgs
+
+
+# --------------------------------------------------------------------------
+# the video loop
+
+def _load_overfit(model, cur: dict, prev: Optional[dict]) -> None:
+    """train_video_Compress.py:51-80: parameters from the overfit checkpoint; a
+    delta model gets current - previous, and the PREVIOUS frame's parameters
+    in its p_* buffers.  The reference as written stores the CURRENT frame's
+    (its :65-71 reads pretrained_dict, the current checkpoint), so its delta
+    model starts at 2 current - previous; that is not reproduced here."""
+    sd = model.state_dict()
+    names = ("_xyz", "_cholesky", "_features_dc")
+    for k in names:
+        if k not in cur:
+            continue
+        v = cur[k].to(sd[k].device, torch.float32)
+        if prev is not None:
+            p = prev[k].to(sd[k].device, torch.float32)[: v.shape[0]]
+            sd["p" + k] = p
+            v = v - p
+        sd[k] = v
+    model.load_state_dict(sd)
+
+
+def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: Sequence[int] = (1,),
+                   iterations: int = 30000, lr: float = 1e-3, device="cuda:0", loss_type="L2",
+                   delta_base: str = "overfit", seed: Optional[int] = None) -> dict:
+    """Fine-tune every overfit frame model of ``state_dict`` (``frame_<i>`` ->
+    {_xyz, _cholesky, _features_dc}, i from 1) under quantization against
+    ``frames`` ([1,3,H,W] each) and encode it: frames listed in ``K_frames``
+    (1-based) as key frames, the others as deltas on the frame before.
+
+    ``delta_base="overfit"`` is the reference: a delta is trained against the
+    previous frame's UNQUANTIZED overfit parameters
+    (train_video_Compress.py:65-71), which a decoder never has, so frames
+    decoded in sequence drift from the trained renders by the previous frames'
+    quantization error.  ``"decoded"`` trains each delta against
+    what the decoder holds -- the previous frame's decoded parameters -- and
+    then ``decode_frames`` reproduces the trained eval renders bit for bit.
+
+    Returns {"streams", "psnr", "bpp" (fixed-length), "bpp_entropy_estimate",
+    "state_dicts"}; the best-PSNR state of each frame is kept, as the reference
+    does."""
+    if delta_base not in ("overfit", "decoded"):
+        raise ValueError("delta_base is 'overfit' or 'decoded'")
+    if seed is not None:
+        torch.manual_seed(seed)
+    device = torch.device(device)
+    streams: List[bytes] = []
+    psnrs, bpps, bpps_est, sds = [], [], [], {}
+    decoded_prev = None
+    for i, gt in enumerate(frames):
+        num = i + 1
+        cur = state_dict[f"frame_{num}"]
+        key = num in K_frames or i == 0
+        gt = gt.to(device)
+        H, W = gt.shape[-2], gt.shape[-1]
+        cls = GaussianVideoFrameQ if key else GaussianVideoDelta
+        model = cls(loss_type=loss_type, opt_type="adan", num_points=cur["_xyz"].shape[0], H=H, W=W,
+                    BLOCK_H=16, BLOCK_W=16, device=device, lr=lr, quantize=True).to(device)
+        prev = None
+        if not key:
+            if delta_base == "decoded":
+                prev = dict(zip(("_xyz", "_cholesky", "_features_dc"), decoded_prev))
+            else:
+                prev = state_dict[f"frame_{num - 1}"]
+        _load_overfit(model, cur, prev)
+        model._init_data()
+        model.train()
+        best_psnr, best_sd = -math.inf, None
+        for _ in range(int(iterations)):
+            _, psnr = model.train_iter_quantize(gt)
+            if psnr > best_psnr:
+                best_psnr, best_sd = psnr, copy.deepcopy(model.state_dict())
+        if best_sd is not None:
+            model.load_state_dict(best_sd)
+        model.eval()
+        with torch.no_grad():
+            out = model.forward_quantize()
+            mse = F.mse_loss(out["render"].float(), gt.float()).item()
+        psnrs.append(10 * math.log10(1.0 / mse) if mse > 0 else math.inf)
+        bpps.append(sum(b.fixed for b in out["unit_bit"]) / H / W)
+        bpps_est.append(sum(b.entropy_estimate for b in out["unit_bit"]) / H / W)
+        streams.append(encode_frame(model))
+        sds[f"frame_{num}"] = {k: v for k, v in model.state_dict().items()
+                               if k in ("_xyz", "_cholesky", "_features_dc")}
+        if delta_base == "decoded":
+            dprev = None if key else decoded_prev
+            if device.type == "cuda":
+                xq, _, cq, Lpre, _, _ = unpack_frames([streams[-1]], device,
+                                                      model.cholesky_bound, prev=dprev)
+                decoded_prev = (xq, Lpre, cq)
+            else:
+                p = None if dprev is None else tuple(t.cpu().numpy() for t in dprev)
+                xq, _, cq, Lpre = unpack_frames_host([streams[-1]], prev=p)[0]
+                decoded_prev = tuple(torch.from_numpy(np.ascontiguousarray(t)) for t in (xq, Lpre, cq))
+    return {"streams": streams, "psnr": psnrs, "bpp": bpps, "bpp_entropy_estimate": bpps_est,
+            "state_dicts": sds}
+
+
+__all__ = ["GaussianVideoFrameQ", "GaussianVideoDelta", "Bits", "encode_frame", "decode_frames",
+           "unpack_frames", "unpack_frames_host", "pack_planes_host", "parse_header",
+           "compress_video", "HEADER_BYTES", "SPLAT_BYTES", "STREAM_MAGIC", "STREAM_VERSION"]

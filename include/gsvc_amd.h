@@ -663,6 +663,82 @@ int gsvc_ssim_backward(int batch, int channels, int height, int width, const flo
                        void *ws, size_t ws_bytes, void *scratch, size_t scratch_bytes,
                        void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Compression stage (GaussianSplats_Compress.py forward_quantize over
+ * quantize.py; DESIGN.md section 13 has the op orders bit-exactness rests on).
+ *
+ * Quantized parameters of one frame model, all fp32 contiguous:
+ *   xq [N,2] = float(half(xyz)) (+ p_xyz), before tanh;
+ *   Lq [N,3] = ((q * scale + beta) + cholesky_bound) (+ p_cholesky) with
+ *              q = round_half_even(clamp((cholesky - beta) / scale, 0, 63));
+ *   cq [N,3] = (e0 + e1) (+ p_features): the nearest codeword of
+ *              codebooks[0] to f and of codebooks[1] to f - e0 (squared
+ *              distance summed over d ascending, lowest index of equal ones);
+ *   codes_chol [N,3], codes_rgb [N,2]: uint8.
+ * scale, beta, cholesky_bound: [3]; codebooks: [2][8][3].  p_xyz, p_cholesky,
+ * p_features: the previous frame's parameters of a delta frame, all three or
+ * all NULL.  commit_sums (optional, [2]): per stage, the sum over splats of
+ * the squared distance to the chosen codeword, reduced in a fixed order
+ * through `workspace` (gsvc_quant_workspace_bytes; only read when commit_sums
+ * is set).  N = 0 launches nothing. */
+size_t gsvc_quant_workspace_bytes(int num_points);
+int gsvc_quant_params_forward(
+    int num_points, const float *xyz, const float *cholesky, const float *features,
+    const float *scale, const float *beta, const float *codebooks, const float *cholesky_bound,
+    const float *p_xyz, const float *p_cholesky, const float *p_features, float *xq, float *Lq,
+    float *cq, unsigned char *codes_chol, unsigned char *codes_rgb, float *commit_sums,
+    void *workspace, size_t workspace_bytes, void *stream);
+
+/* Straight-through backward of the above.  With raw = (cholesky - beta) / scale,
+ * mask = (0 <= raw <= 63), q = round(clamp(raw)):
+ *   v_xyz = v_xq;  v_cholesky = v_Lq * mask;
+ *   v_scale[k] = sum_n v_Lq * (q - mask * raw);  v_beta[k] = sum_n v_Lq * (1 - mask);
+ *   v_features = 2 * v_cq + (v_commit[0] * 2 (f - e0) + v_commit[1] * 2 ((f - e0) - e1)).
+ * v_commit ([2], optional): the gradients of commit_sums; NULL drops the term
+ * (features, codebooks and codes_rgb are then not read).  codes_rgb: the
+ * forward's.  v_scale, v_beta ([3] each) are reduced in a fixed order, no
+ * float atomics: equal inputs give equal bits. */
+int gsvc_quant_params_backward(
+    int num_points, const float *cholesky, const float *features, const float *scale,
+    const float *beta, const float *codebooks, const unsigned char *codes_rgb, const float *v_xq,
+    const float *v_Lq, const float *v_cq, const float *v_commit, float *v_xyz, float *v_cholesky,
+    float *v_features, float *v_scale, float *v_beta, void *workspace, size_t workspace_bytes,
+    void *stream);
+
+/* The packed stream of one frame, little-endian, GSVC_STREAM_HEADER_BYTES +
+ * GSVC_STREAM_SPLAT_BYTES * N bytes:
+ *   header: u32 magic, u32 version, i32 N, u32 H, u32 W, u32 flags (bit 0: a
+ *           delta frame), f32 scale[3], beta[3], codebooks[48]; zero to the end;
+ *   plane A, N x 4 bytes: half(x), half(y);
+ *   plane B, N x 3 bytes: c0 | c1 << 6 | c2 << 12 | i0 << 18 | i1 << 21.
+ * gsvc_pack_splats writes the two planes (7 N bytes at `planes`) from xyz and
+ * the forward's codes; the caller writes the header. */
+#define GSVC_STREAM_MAGIC 0x51565347u /* "GSVQ" */
+#define GSVC_STREAM_VERSION 1
+#define GSVC_STREAM_HEADER_BYTES 256
+#define GSVC_STREAM_SPLAT_BYTES 7
+int gsvc_pack_splats(int num_points, const float *xyz, const unsigned char *codes_chol,
+                     const unsigned char *codes_rgb, unsigned char *planes, void *stream);
+
+/* Decodes num_frames concatenated frame streams in one launch to xq, Lq, cq
+ * (frame f's splats follow frame f-1's; the bits of the forward entry above
+ * for the same half / codes / tables).  stream_host: the bytes in host memory,
+ * validated before any launch (magic, version, N >= 0, each frame's length
+ * against frame_offsets [num_frames + 1] host byte offsets, one H x W);
+ * stream_dev: the same bytes in device memory, which the kernel reads.  A
+ * delta frame adds the decoded pre-activation parameters of the frame before
+ * it (its first N splats; N may not exceed that frame's count): frame f-1 of
+ * this call, or for frame 0 prev_xyz / prev_cholesky / prev_features
+ * [prev_points] -- xq, Lpre and cq of the previous call's last frame.  A
+ * delta frame 0 with prev_points = 0 is an error.  Lpre (optional, [total,3]):
+ * Lq without cholesky_bound.  out_capacity: splats the outputs hold. */
+int gsvc_unpack_splats(int num_frames, const unsigned char *stream_host,
+                       const long long *frame_offsets, const unsigned char *stream_dev,
+                       const float *cholesky_bound, const float *prev_xyz,
+                       const float *prev_cholesky, const float *prev_features, int prev_points,
+                       float *xq, float *Lq, float *cq, float *Lpre, long long out_capacity,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
