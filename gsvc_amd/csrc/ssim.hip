@@ -310,20 +310,22 @@ __global__ __launch_bounds__(256) void ssim_reduce_kernel(const float2 *__restri
 // Values (out[1] when size_average, else out[B]) and per-(level, plane)
 // upstream factors {d value / d ssim_map pixel, d value / d cs pixel} per unit
 // of the caller's output gradient.  flags: bit0 size_average, bit1
-// nonnegative_ssim (single level).  A thread per plane forms its value in fp32
-// as the package does (relu, ** weights, product); thread 0 then takes the
-// means over planes in double, in plane order.
+// nonnegative_ssim (ssim() only), bit2 the multi-scale formula (ms_ssim(); any
+// call with more than one level takes it too, so a single weight w gives
+// relu(ssim) ** w and not the plain SSIM).  A thread per plane forms its value
+// in fp32 as the package does (relu, ** weights, product); thread 0 then takes
+// the means over planes in double, in plane order.
 __global__ __launch_bounds__(256) void ssim_combine_kernel(const double2 *__restrict__ stats,
                                                            SsimLevels L, int batch, int channels,
                                                            int flags, float *__restrict__ out,
                                                            float2 *__restrict__ fac,
                                                            float *__restrict__ vals) {
     const int planes = batch * channels;
-    const bool avg = flags & 1, nonneg = flags & 2;
+    const bool avg = flags & 1, nonneg = flags & 2, multi = (flags & 4) || L.n > 1;
     const float scale = avg ? 1.0f / (float)planes : 1.0f / (float)channels;
     for (int p = threadIdx.x; p < planes; p += blockDim.x) {
         float val;
-        if (L.n == 1) {
+        if (!multi) {
             const float s = (float)stats[p].x;
             val = (nonneg && s < 0.0f) ? 0.0f : s;
             const float d = (nonneg && s <= 0.0f) ? 0.0f : scale;

@@ -9,8 +9,11 @@ published signatures, checks and arithmetic (Gaussian window, valid separable
 filtering, C1/C2, per-channel means, the 5-level average-pool pyramid with
 relu'd cs / ssim terms) and run them as the kernels of csrc/ssim.hip, forward
 and backward, without a host sync.  Parity is against oracle/oracle.py's
-float64 restatement and a torch fp32 restatement (tests/test_ssim.py):
-"parity unpinned" against the package itself.
+float64 restatement and a torch restatement (tests/test_ssim.py,
+tests/test_ssim_edges.py): "parity unpinned" against the package itself
+(DESIGN.md §2).  Where a relu'd term clamps (a level of ms_ssim, or
+nonnegative_ssim) the plane's gradient is 0 (relu'(0) = 0); autograd through
+ms_ssim's 0 ** (w - 1) gives NaN there.
 
 CUDA (HIP) tensors only: there is no CPU fallback.  3-D volumes (5-d input)
 and custom ``win`` tensors are not provided.
@@ -134,7 +137,7 @@ def ms_ssim(X: Tensor, Y: Tensor, data_range: float = 255, size_average: bool = 
     if not 1 <= len(weights) <= 8:
         raise NotImplementedError("gsvc_amd.msssim: 1 to 8 levels")
     C1, C2 = _consts(data_range, K)
-    flags = 1 if size_average else 0
+    flags = (1 if size_average else 0) | 4  # bit2: the multi-scale formula, also for one weight
     return _SsimFn.apply(X, Y, int(win_size), float(win_sigma), C1, C2, weights, flags)
 
 

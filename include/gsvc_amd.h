@@ -641,9 +641,13 @@ int gsvc_i420_to_rgb(const unsigned char *yuv, int height, int width, float *out
  * per-frame MS-SSIM metric, train_video_Represent.py:145), restating
  * pytorch_msssim's ssim() / ms_ssim() (_ssim, gaussian_filter, avg-pool
  * pyramid).  X, Y: [batch*channels][H][W] fp32 device planes.  levels = 1:
- * ssim(); levels > 1: ms_ssim() with `weights` (host, levels values).
+ * ssim() (or, with flag bit2, ms_ssim() with one weight); levels > 1: ms_ssim()
+ * with `weights` (host, levels values).
  * flags: bit0 size_average (out[1]; else out[batch] = mean over channels),
- * bit1 nonnegative_ssim (levels = 1).  C1 = (K1 data_range)^2, C2 = (K2 data_range)^2.
+ * bit1 nonnegative_ssim (ssim() only), bit2 the multi-scale formula
+ * prod_i relu(term_i)^weights[i] (implied by levels > 1; with levels = 1 it is
+ * ms_ssim() with a single weight, relu(ssim)^weights[0], where levels = 1
+ * without it is ssim()).  C1 = (K1 data_range)^2, C2 = (K2 data_range)^2.
  * The forward leaves in `ws` what the backward needs (pooled levels, upstream
  * factors): pass the same workspace to the backward.  win_size odd, <= 11. */
 size_t gsvc_ssim_workspace_bytes(int planes, int height, int width, int win_size, int levels);

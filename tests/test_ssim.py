@@ -8,11 +8,13 @@ algorithm -- the float64 oracle (oracle/oracle.py ssim/ms_ssim) and a torch
 fp32 one below (F.conv2d with grouped 1-D Gaussian windows, F.avg_pool2d),
 which also gives the autograd gradients the HIP backward is checked against.
 
-CPU: the two restatements agree; argument checks.  GPU: values vs the oracle
-(abs 2e-5: fp32 filtering vs float64), gradients w.r.t. X and Y vs torch
-autograd of the fp32 restatement (relative to the largest element, 1e-3),
-1080p, odd sizes, window 5, dimensions shorter than the window, per-image
-output, the loss_fn variants end to end.
+CPU: the two restatements agree; argument checks.  GPU: values vs the oracle,
+gradients w.r.t. X and Y vs torch autograd of the fp32 restatement on the GPU
+(relative to the largest element), 1080p, odd sizes, window 5, dimensions
+shorter than the window, per-image output, the loss_fn variants end to end.
+Tile edges, the other windows, clamps and options: test_ssim_edges.py, whose
+measured bars (BAR below) hold here too; the gradient reference of this module
+is itself fp32, so its bar adds that reference's own worst error (GRAD_BAR).
 """
 import numpy as np
 import pytest
@@ -20,6 +22,20 @@ import torch
 import torch.nn.functional as F
 
 from conftest import REPO  # noqa: F401
+
+
+# The fp32 restatement's worst error against the float64 references over the
+# cases of ssim_cases.py, on the CPU (tests/analysis/ssim_bars.py prints them):
+# family -> (value, absolute; gradient, relative to the largest element).  The
+# kernels' bar is 4 times that: their summation order and fma contraction differ.
+RESTATEMENT_WORST = {
+    "ssim": (2.54e-7, 4.68e-6),
+    "ms": (8.88e-7, 2.65e-5),
+    "r255": (7.80e-7, 2.06e-5),   # data_range 255: E[x^2] - mu^2 cancels at 255^2
+}
+BAR = {fam: (4 * v, 4 * g) for fam, (v, g) in RESTATEMENT_WORST.items()}
+# against fp32 autograd instead of float64: the bar plus the reference's own error
+GRAD_BAR = {fam: BAR[fam][1] + RESTATEMENT_WORST[fam][1] for fam in ("ssim", "ms")}
 
 
 # ---------------------------------------------------------------- torch fp32 restatement
@@ -137,7 +153,7 @@ def test_ssim_matches_oracle(cuda, oracle, shape, win, avg, nonneg):
                nonnegative_ssim=nonneg)
     ref = oracle.ssim(X.numpy(), Y.numpy(), 1.0, size_average=avg, win_size=win,
                       nonnegative_ssim=nonneg)
-    np.testing.assert_allclose(got.cpu().double().numpy(), ref, rtol=0, atol=2e-5)
+    np.testing.assert_allclose(got.cpu().double().numpy(), ref, rtol=0, atol=BAR["ssim"][0])
 
 
 @pytest.mark.gpu
@@ -150,10 +166,10 @@ def test_ms_ssim_matches_oracle(cuda, oracle, shape, win, avg):
     X, Y = _pair(shape, 4)
     got = ms_ssim(X.to(cuda), Y.to(cuda), data_range=1, size_average=avg, win_size=win)
     ref = oracle.ms_ssim(X.numpy(), Y.numpy(), 1.0, size_average=avg, win_size=win)
-    np.testing.assert_allclose(got.cpu().double().numpy(), ref, rtol=0, atol=2e-5)
+    np.testing.assert_allclose(got.cpu().double().numpy(), ref, rtol=0, atol=BAR["ms"][0])
 
 
-def _grad_close(got, ref, tol=1e-3):
+def _grad_close(got, ref, tol):
     scale = float(ref.abs().max())
     err = float((got - ref).abs().max())
     assert err <= tol * scale, (err, scale)
@@ -178,8 +194,9 @@ def test_gradients_match_torch_autograd(cuda, multi, shape, win):
     w = torch.linspace(0.5, 1.5, a.numel(), device=cuda)  # distinct per-image upstream
     (a * w).sum().backward()
     (r * w).sum().backward()
-    _grad_close(xa.grad, xr.grad)
-    _grad_close(ya.grad, yr.grad)
+    tol = GRAD_BAR["ms" if multi else "ssim"]
+    _grad_close(xa.grad, xr.grad, tol)
+    _grad_close(ya.grad, yr.grad, tol)
 
 
 @pytest.mark.gpu
@@ -204,5 +221,6 @@ def test_loss_fn_ssim_variants(cuda, loss_type):
         lr = lam * F.l1_loss(pr, gt) + (1 - lam) * (1 - t_ms_ssim(pr, gt, win_size=5))
     la.backward()
     lr.backward()
+    multi = loss_type in ("Fusion4", "Fusion_hinerv")
     assert abs(float(la) - float(lr)) < 2e-5
-    _grad_close(pa.grad, pr.grad)
+    _grad_close(pa.grad, pr.grad, GRAD_BAR["ms" if multi else "ssim"])
