@@ -120,6 +120,9 @@ _SIGS = {
     "gsvc_quant_params_backward": [_I] + [_P] * 15 + [_P, _SZ, _P],
     "gsvc_pack_splats": [_I, _P, _P, _P, _P, _P],
     "gsvc_unpack_splats": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _LL, _P],
+    "gsvc_stream_expanded_bytes": [_I, _P, _P, _P],
+    "gsvc_expand_stream": [_I, _P, _P, _P, _P, _SZ, _P],
+    "gsvc_unpack_stream": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _LL, _P, _SZ, _P],
 }
 # include/gsvc_amd_diag.h: the diagnostic library's extra entry points
 _DIAG_SIGS = {

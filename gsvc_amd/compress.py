@@ -12,9 +12,10 @@ render and its backward are the existing operators, the optimizer the existing
 ``Adan``.
 
 ``encode_frame`` writes a model as the fixed-length stream of
-include/gsvc_amd.h (256-byte header + 7 bytes per splat), ``decode_frames``
-turns a list of such streams into images with one unpack launch and
-``render_frames_sum``; ``compress_video`` is the loop of
+include/gsvc_amd.h (256-byte header + 7 bytes per splat) or, with
+``entropy=True``, as its entropy-coded transcoding (version 2, ans.py);
+``decode_frames`` turns a list of such streams, of either version, into images
+with one expand and one unpack launch and ``render_frames_sum``; ``compress_video`` is the loop of
 train_video_Compress.py:240-271 without its image and video writing.
 """
 from __future__ import annotations
@@ -32,9 +33,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
+from . import ans
 from .adan import Adan
 from .frame import loss_fn
 from .project_gaussians_2d import project_gaussians_2d
+from .ans import entropy_code, entropy_expand
 from .quantize import (FakeQuantizationHalf, ResidualVQ8, UniformQuantizer, fixed_bits,
                        quantize_params, vq_loss_from_sums, zeroth_order_bits, _table_bits)
 from .rasterize_sum import rasterize_gaussians_sum
@@ -42,6 +45,7 @@ from .render import render_frame_sum, render_frames_sum
 
 STREAM_MAGIC = 0x51565347  # "GSVQ"
 STREAM_VERSION = 1
+STREAM_VERSION_CODED = 2  # the entropy-coded transcoding of version 1 (ans.py)
 HEADER_BYTES = 256
 SPLAT_BYTES = 7
 _HEADER = struct.Struct("<IIiIII3f3f48f")  # magic, version, N, H, W, flags, scale, beta, codebooks
@@ -210,21 +214,27 @@ def _header(n, H, W, delta, scale, beta, codebooks) -> bytes:
 
 
 def parse_header(buf) -> dict:
-    """Fields of one frame stream's header; raises ValueError on a wrong magic,
-    version, length or N."""
+    """Fields of one frame stream's header, of either version (``version``; a
+    version-2 header also gives ``S``, ``n_seg`` and ``payload_bytes``); raises
+    ValueError on a wrong magic, version, length or N, and for version 2 on
+    whatever ``ans.parse_coded`` refuses."""
     if len(buf) < HEADER_BYTES:
         raise ValueError(f"stream truncated: {len(buf)} bytes, the header is {HEADER_BYTES}")
     f = _HEADER.unpack_from(buf, 0)
     if f[0] != STREAM_MAGIC:
         raise ValueError(f"wrong magic 0x{f[0]:08x}")
-    if f[1] != STREAM_VERSION:
-        raise ValueError(f"stream version {f[1]}, not {STREAM_VERSION}")
+    if f[1] not in (STREAM_VERSION, STREAM_VERSION_CODED):
+        raise ValueError(f"stream version {f[1]}, not {STREAM_VERSION} or {STREAM_VERSION_CODED}")
     n = f[2]
-    if n < 0 or len(buf) != HEADER_BYTES + SPLAT_BYTES * n:
+    extra = {}
+    if f[1] == STREAM_VERSION_CODED:
+        coded = ans.parse_coded(buf)
+        extra = {k: coded[k] for k in ("S", "n_seg", "payload_bytes")}
+    elif n < 0 or len(buf) != HEADER_BYTES + SPLAT_BYTES * n:
         raise ValueError(f"stream of {len(buf)} bytes does not hold N = {n} splats")
     return dict(N=n, H=f[3], W=f[4], delta=bool(f[5] & FLAG_DELTA),
                 scale=np.array(f[6:9], np.float32), beta=np.array(f[9:12], np.float32),
-                codebooks=np.array(f[12:60], np.float32).reshape(2, 8, 3))
+                codebooks=np.array(f[12:60], np.float32).reshape(2, 8, 3), version=f[1], **extra)
 
 
 def pack_planes_host(xyz, codes_chol, codes_rgb) -> bytes:
@@ -238,9 +248,10 @@ def pack_planes_host(xyz, codes_chol, codes_rgb) -> bytes:
     return a + b.reshape(n * 3).tobytes()
 
 
-def encode_frame(model) -> bytes:
-    """The model's quantized parameters as one frame stream:
-    ``256 + 7 * N`` bytes."""
+def encode_frame(model, entropy: bool = False, segment: int = 32) -> bytes:
+    """The model's quantized parameters as one frame stream: ``256 + 7 * N``
+    bytes, or with ``entropy`` their entropy-coded transcoding in segments of
+    ``segment`` splats (``ans.entropy_code``)."""
     with torch.no_grad():
         _, _, _, codes_chol, codes_rgb, _ = model.quantized(commit=False)
         xyz = model._xyz.detach().float().contiguous()
@@ -255,7 +266,7 @@ def encode_frame(model) -> bytes:
             body = planes.cpu().numpy().tobytes()
         else:
             body = pack_planes_host(xyz.numpy(), codes_chol.numpy(), codes_rgb.numpy())
-    return head + body
+    return ans.entropy_code(head + body, segment) if entropy else head + body
 
 
 def unpack_frames_host(streams: Sequence[bytes], cholesky_bound=(0.5, 0.0, 0.5), prev=None):
@@ -266,6 +277,8 @@ def unpack_frames_host(streams: Sequence[bytes], cholesky_bound=(0.5, 0.0, 0.5),
     out = []
     for k, buf in enumerate(streams):
         h = parse_header(buf)
+        if h["version"] == STREAM_VERSION_CODED:
+            buf = ans.entropy_expand(buf)
         n = h["N"]
         a = np.frombuffer(buf, "<f2", count=2 * n, offset=HEADER_BYTES).reshape(n, 2)
         b = np.frombuffer(buf, np.uint8, count=3 * n, offset=HEADER_BYTES + 4 * n).reshape(n, 3)
@@ -290,7 +303,10 @@ def unpack_frames_host(streams: Sequence[bytes], cholesky_bound=(0.5, 0.0, 0.5),
 def unpack_frames(streams: Sequence[bytes], device, cholesky_bound=None, prev=None):
     """One gsvc_unpack_splats launch for the concatenated frame streams:
     ``(xq, Lq, cq, Lpre, sizes, (H, W))`` with the frames' splats concatenated.
-    ``prev`` = (xq, Lpre, cq) of the frame before the first (device tensors)."""
+    ``prev`` = (xq, Lpre, cq) of the frame before the first (device tensors).
+    A list that holds entropy-coded frames goes through gsvc_unpack_stream: one
+    launch expands every frame to version-1 bytes on the device, then the same
+    walk runs on those."""
     device = torch.device(device)
     blob = b"".join(streams)
     offs = [0]
@@ -314,14 +330,20 @@ def unpack_frames(streams: Sequence[bytes], device, cholesky_bound=None, prev=No
     if prev is not None:
         p = [t.detach().to(device=device, dtype=torch.float32).contiguous() for t in prev]
         prev_n = p[0].shape[0]
-    L.call("gsvc_unpack_splats", len(streams), ctypes.c_char_p(blob), offs_c, L.ptr(dev_stream),
-           L.ptr(bound), L.ptr(p[0]), L.ptr(p[1]), L.ptr(p[2]), prev_n, L.ptr(xq), L.ptr(Lq),
-           L.ptr(cq), L.ptr(Lpre), total, L.stream(device))
+    args = (len(streams), ctypes.c_char_p(blob), offs_c, L.ptr(dev_stream), L.ptr(bound), L.ptr(p[0]),
+            L.ptr(p[1]), L.ptr(p[2]), prev_n, L.ptr(xq), L.ptr(Lq), L.ptr(cq), L.ptr(Lpre), total)
+    if any(h["version"] == STREAM_VERSION_CODED for h in heads):
+        work = torch.empty((HEADER_BYTES * len(streams) + SPLAT_BYTES * total,), dtype=torch.uint8,
+                           device=device)
+        L.call("gsvc_unpack_stream", *args, L.ptr(work), work.numel(), L.stream(device))
+    else:
+        L.call("gsvc_unpack_splats", *args, L.stream(device))
     return xq, Lq, cq, Lpre, sizes, (int(hw[0]), int(hw[1]))
 
 
 def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: bool = False):
-    """Frame streams (``encode_frame``) to images [F, 3, H, W].
+    """Frame streams (``encode_frame``, either version, in any mix) to images
+    [F, 3, H, W].
 
     On a HIP device: one unpack launch for all frames, then
     ``render_frames_sum``.  A delta frame adds the DECODED parameters of the
@@ -383,7 +405,8 @@ def _load_overfit(model, cur: dict, prev: Optional[dict]) -> None:
 
 def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: Sequence[int] = (1,),
                    iterations: int = 30000, lr: float = 1e-3, device="cuda:0", loss_type="L2",
-                   delta_base: str = "overfit", seed: Optional[int] = None) -> dict:
+                   delta_base: str = "overfit", seed: Optional[int] = None, entropy: bool = False,
+                   segment: int = 32) -> dict:
     """Fine-tune every overfit frame model of ``state_dict`` (``frame_<i>`` ->
     {_xyz, _cholesky, _features_dc}, i from 1) under quantization against
     ``frames`` ([1,3,H,W] each) and encode it: frames listed in ``K_frames``
@@ -399,14 +422,15 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
 
     Returns {"streams", "psnr", "bpp" (fixed-length), "bpp_entropy_estimate",
     "state_dicts"}; the best-PSNR state of each frame is kept, as the reference
-    does."""
+    does.  With ``entropy`` the streams are entropy-coded (version 2, segments
+    of ``segment`` splats) and "bpp_coded" gives their ``8 * len / (H * W)``."""
     if delta_base not in ("overfit", "decoded"):
         raise ValueError("delta_base is 'overfit' or 'decoded'")
     if seed is not None:
         torch.manual_seed(seed)
     device = torch.device(device)
     streams: List[bytes] = []
-    psnrs, bpps, bpps_est, sds = [], [], [], {}
+    psnrs, bpps, bpps_est, bpps_coded, sds = [], [], [], [], {}
     decoded_prev = None
     for i, gt in enumerate(frames):
         num = i + 1
@@ -440,7 +464,8 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
         psnrs.append(10 * math.log10(1.0 / mse) if mse > 0 else math.inf)
         bpps.append(sum(b.fixed for b in out["unit_bit"]) / H / W)
         bpps_est.append(sum(b.entropy_estimate for b in out["unit_bit"]) / H / W)
-        streams.append(encode_frame(model))
+        streams.append(encode_frame(model, entropy=entropy, segment=segment))
+        bpps_coded.append(8 * len(streams[-1]) / H / W)
         sds[f"frame_{num}"] = {k: v for k, v in model.state_dict().items()
                                if k in ("_xyz", "_cholesky", "_features_dc")}
         if delta_base == "decoded":
@@ -453,10 +478,14 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
                 p = None if dprev is None else tuple(t.cpu().numpy() for t in dprev)
                 xq, _, cq, Lpre = unpack_frames_host([streams[-1]], prev=p)[0]
                 decoded_prev = tuple(torch.from_numpy(np.ascontiguousarray(t)) for t in (xq, Lpre, cq))
-    return {"streams": streams, "psnr": psnrs, "bpp": bpps, "bpp_entropy_estimate": bpps_est,
-            "state_dicts": sds}
+    out = {"streams": streams, "psnr": psnrs, "bpp": bpps, "bpp_entropy_estimate": bpps_est,
+           "state_dicts": sds}
+    if entropy:
+        out["bpp_coded"] = bpps_coded
+    return out
 
 
 __all__ = ["GaussianVideoFrameQ", "GaussianVideoDelta", "Bits", "encode_frame", "decode_frames",
            "unpack_frames", "unpack_frames_host", "pack_planes_host", "parse_header",
-           "compress_video", "HEADER_BYTES", "SPLAT_BYTES", "STREAM_MAGIC", "STREAM_VERSION"]
+           "compress_video", "HEADER_BYTES", "SPLAT_BYTES", "STREAM_MAGIC", "STREAM_VERSION",
+           "STREAM_VERSION_CODED", "entropy_code", "entropy_expand"]

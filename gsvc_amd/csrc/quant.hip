@@ -21,7 +21,7 @@
 // kQuantMaxBlocks blocks strides over N), a wave folds by xor-shuffles 32..1,
 // lane 0..K-1 of the block adds the 4 wave sums in order and stores the block
 // partial, and a second one-block launch adds the partials in block order.
-#include "common.h"
+#include "stream.h"
 
 namespace gsvc {
 
@@ -31,12 +31,7 @@ constexpr int kQuantSums = 8;  // floats per block partial (6 used by the backwa
 constexpr int kQMax = 63;      // 6-bit codes
 constexpr int kCodewords = 8, kStages = 2;
 
-constexpr unsigned kStreamMagic = GSVC_STREAM_MAGIC;
-constexpr int kHeaderBytes = GSVC_STREAM_HEADER_BYTES;
-constexpr int kSplatBytes = GSVC_STREAM_SPLAT_BYTES;
-// header field offsets (include/gsvc_amd.h)
-constexpr int kOffMagic = 0, kOffVersion = 4, kOffN = 8, kOffH = 12, kOffW = 16, kOffFlags = 20,
-              kOffScale = 24, kOffBeta = 36, kOffCodebooks = 48;
+// stream layout: stream.h
 static_assert(kOffCodebooks + 4 * 3 * kStages * kCodewords <= kHeaderBytes, "header layout");
 
 static int quant_blocks(int n) { return n < 1 ? 1 : std::min(ceil_div(n, kQuantBlock), kQuantMaxBlocks); }
@@ -273,10 +268,6 @@ __global__ __launch_bounds__(kQuantBlock) void pack_kernel(
     b[2] = (unsigned char)((w >> 16) & 0xff);
 }
 
-// little-endian reads at any byte offset
-__device__ __forceinline__ unsigned rd_u32(const unsigned char *p) {
-    return (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16 | (unsigned)p[3] << 24;
-}
 __device__ __forceinline__ float rd_f32(const unsigned char *p) {
     return __uint_as_float(rd_u32(p));
 }
@@ -349,6 +340,19 @@ __global__ __launch_bounds__(kQuantBlock) void unpack_kernel(
         off += kHeaderBytes + kSplatBytes * n;
         so += n;
     }
+}
+
+// the walk's launch, for gsvc_unpack_splats and gsvc_unpack_stream (stream.h)
+int launch_unpack_walk(const char *what, int num_frames, const unsigned char *stream_dev,
+                       long long total_bytes, long long total_splats, long long nmax,
+                       const float *cholesky_bound, const float *prev_xyz,
+                       const float *prev_cholesky, const float *prev_features, int prev_points,
+                       float *xq, float *Lq, float *cq, float *Lpre, hipStream_t s) {
+    if (nmax > 0x7fffffffll - kQuantBlock) return set_error(GSVC_ERR_ARG, "%s: frame too large", what);
+    hipLaunchKernelGGL(unpack_kernel, dim3(ceil_div((int)nmax, kQuantBlock)), dim3(kQuantBlock), 0, s,
+                       num_frames, stream_dev, total_bytes, total_splats, cholesky_bound, prev_xyz,
+                       prev_cholesky, prev_features, prev_points, xq, Lq, cq, Lpre);
+    return check_launch(what);
 }
 
 }  // namespace gsvc
@@ -444,9 +448,7 @@ extern "C" int gsvc_pack_splats(int num_points, const float *xyz, const unsigned
     return check_launch("pack_splats");
 }
 
-static unsigned host_u32(const unsigned char *p) {
-    return (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16 | (unsigned)p[3] << 24;
-}
+static unsigned host_u32(const unsigned char *p) { return rd_u32(p); }
 
 extern "C" int gsvc_unpack_splats(int num_frames, const unsigned char *stream_host,
                                   const long long *frame_offsets, const unsigned char *stream_dev,
@@ -502,10 +504,7 @@ extern "C" int gsvc_unpack_splats(int num_frames, const unsigned char *stream_ho
     if (total == 0) return GSVC_OK;
     if (!stream_dev || !cholesky_bound || !xq || !Lq || !cq)
         return set_error(GSVC_ERR_ARG, "unpack_splats: null tensor");
-    if (nmax > 0x7fffffffll - kQuantBlock) return set_error(GSVC_ERR_ARG, "unpack_splats: frame too large");
-    hipLaunchKernelGGL(unpack_kernel, dim3(ceil_div((int)nmax, kQuantBlock)), dim3(kQuantBlock), 0,
-                       (hipStream_t)stream, num_frames, stream_dev, frame_offsets[num_frames], total,
-                       cholesky_bound, prev_xyz, prev_cholesky, prev_features, prev_points, xq, Lq, cq,
-                       Lpre);
-    return check_launch("unpack_splats");
+    return launch_unpack_walk("unpack_splats", num_frames, stream_dev, frame_offsets[num_frames], total,
+                              nmax, cholesky_bound, prev_xyz, prev_cholesky, prev_features, prev_points,
+                              xq, Lq, cq, Lpre, (hipStream_t)stream);
 }

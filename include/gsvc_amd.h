@@ -743,6 +743,52 @@ int gsvc_unpack_splats(int num_frames, const unsigned char *stream_host,
                        float *xq, float *Lq, float *cq, float *Lpre, long long out_capacity,
                        void *stream);
 
+/* The entropy-coded stream of one frame (version 2), a lossless transcoding of
+ * the version-1 stream above, little-endian:
+ *   bytes 0-239:   the version-1 header with version = GSVC_STREAM_VERSION_CODED;
+ *   bytes 240-255: u16 S (splats per segment, 1..4096), u16 prob_bits (12),
+ *                  u32 n_seg = ceil(N / S), u32 payload_bytes, u32 zero;
+ *   tables, 1440 bytes: for the channels c0, c1, c2 (alphabet 64 each), i0, i1
+ *                  (8 each), high byte of half(x), of half(y) (256 each) the
+ *                  u16 frequencies of the symbols; each channel sums to 4096;
+ *   2 N bytes:     per splat the low byte of half(x), of half(y);
+ *   directory:     n_seg + 1 u32 offsets into the payload: 0 first,
+ *                  payload_bytes last, even, each segment at least 4 bytes;
+ *   payload:       per segment of S splats a u32 rANS state, then the u16 words
+ *                  in the order the decoder consumes them (32-bit state,
+ *                  L = 2^16, splat-major, the seven channels per splat in the
+ *                  order above).
+ * The three entries below take frames of either version in one list and, like
+ * gsvc_unpack_splats, validate the host copy before any launch: everything
+ * above that needs no decoding (not a segment's final state, which only the
+ * host decoder gsvc_amd.ans.entropy_expand checks). */
+#define GSVC_STREAM_VERSION_CODED 2
+
+/* expanded_offsets [num_frames + 1]: the byte offsets the frames have once
+ * every one is expanded to version 1 (256 + 7 N bytes each). */
+int gsvc_stream_expanded_bytes(int num_frames, const unsigned char *stream_host,
+                               const long long *frame_offsets, long long *expanded_offsets);
+
+/* Transcodes the frames at stream_dev to version-1 bytes at expanded_dev
+ * (expanded_capacity bytes; GSVC_ERR_WORKSPACE when they do not fit): one
+ * kernel, one lane per frame and segment; a version-1 frame is copied.  The
+ * kernel re-derives and clamps everything it reads from the device copy, so a
+ * device copy that differs from the validated host copy decodes to other
+ * bytes, not out of bounds. */
+int gsvc_expand_stream(int num_frames, const unsigned char *stream_host,
+                       const long long *frame_offsets, const unsigned char *stream_dev,
+                       unsigned char *expanded_dev, size_t expanded_capacity, void *stream);
+
+/* gsvc_unpack_splats for frames of either version: expands the list into
+ * workspace (workspace_bytes >= expanded_offsets[num_frames]; not used when
+ * every frame is version 1), then runs gsvc_unpack_splats' frame walk on it. */
+int gsvc_unpack_stream(int num_frames, const unsigned char *stream_host,
+                       const long long *frame_offsets, const unsigned char *stream_dev,
+                       const float *cholesky_bound, const float *prev_xyz,
+                       const float *prev_cholesky, const float *prev_features, int prev_points,
+                       float *xq, float *Lq, float *cq, float *Lpre, long long out_capacity,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
