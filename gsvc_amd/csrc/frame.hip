@@ -305,8 +305,12 @@ int frame_project_launch(int n, const float *xyz, int xyz_tanh, const float *cho
                      (long long *)nullptr, frames > 1 ? frame_off : (const int *)nullptr,
                      f.counts_stride, f.m_stride, slab_stride, id_slab, w.ovf);
         timing_end(s, tslot, kTimingProject);
-    } else if (dev_zero(f.m_acc, sizeof(int), s) != GSVC_OK)
+    } else if (dev_zero(f.m_acc < f.m_clear ? f.m_acc : f.m_clear, 2 * sizeof(int), s) != GSVC_OK) {
+        // (no splats, no kernel: this frame's M slot AND the next frame's, which
+        // the kernels' block 0 clears -- left alone it kept the previous frame's
+        // M, and a next frame with M = 0 composited black, not the background)
         return set_error(GSVC_ERR_HIP, "frame projection: memset failed");
+    }
     return check_launch("frame projection");
 }
 

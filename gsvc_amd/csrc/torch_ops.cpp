@@ -411,6 +411,37 @@ std::vector<Tensor> rasterize_sum(Tensor xys, Tensor radii, Tensor conics, Tenso
     return RasterSumFn::apply(xys, radii, conics, colors, opacity, background, H, W, need_grad);
 }
 
+// A read-only window on the carried state of one (device, stream), for tests
+// that must show which state a call ran in: the locks of the call path in its
+// order (registry, then workspace, then hint), no workspace created, no event
+// polled.  found is false (and the fields those of a new workspace) when the
+// pair has not been used yet.
+pybind11::dict op_state(int64_t device, int64_t stream) {
+    SlabWs *ws = nullptr;
+    {
+        std::lock_guard<std::mutex> g(g_ws_lock);
+        const std::pair<int, void *> key((int)device, (void *)(intptr_t)stream);
+        for (auto &kv : g_ws)
+            if (kv.first == key) ws = kv.second.get();
+    }
+    pybind11::dict d;
+    int calls = 0, tiles = -1, order_n = -1, order_age = 0;
+    if (ws) {
+        std::lock_guard<std::mutex> wl(ws->lock);
+        calls = ws->calls;
+        tiles = ws->tiles;
+        order_n = ws->order_n;
+        order_age = ws->order_age;
+    }
+    d["found"] = ws != nullptr;
+    d["calls"] = calls;
+    d["tiles"] = tiles;
+    d["order_n"] = order_n;
+    d["order_age"] = order_age;
+    d["hint"] = hint_cached((int)device);
+    return d;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -420,4 +451,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_sum", &rasterize_sum,
           "rasterize_sum.py:89-254 on the sync-free binning: (out_img, M on the device)");
     m.def("abi_version", []() { return gsvc_abi_version(); });
+    m.def("op_state", &op_state,
+          "read-only: calls, tiles, order_n, order_age of the (device, stream) workspace and the "
+          "device's cached M hint");
 }
