@@ -123,6 +123,8 @@ _SIGS = {
     "gsvc_stream_expanded_bytes": [_I, _P, _P, _P],
     "gsvc_expand_stream": [_I, _P, _P, _P, _P, _SZ, _P],
     "gsvc_unpack_stream": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _LL, _P, _SZ, _P],
+    "gsvc_encode_stream_bytes": [_I, _P, _I, _P, _P],
+    "gsvc_encode_stream": [_I, _P, _P, _I, _P, _SZ, _P, _P, _SZ, _P],
 }
 # include/gsvc_amd_diag.h: the diagnostic library's extra entry points
 _DIAG_SIGS = {
@@ -153,7 +155,7 @@ _RESTYPE = {
     "gsvc_quant_workspace_bytes": _SZ,
 }
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _libs = {}       # path -> loaded CDLL
 _active = None   # the library ops call (load())

@@ -8,7 +8,9 @@ splats cut into segments of S that decode independently; the low bytes of the
 positions are stored raw.  DESIGN.md §13 has the layout, the coder and the
 normalisation rule.  ``entropy_code`` and ``entropy_expand`` are numpy,
 vectorised across segments: one step per symbol position, on all segments at
-once.  The device decoder is csrc/ans.hip (``gsvc_expand_stream``).
+once.  The device decoder is csrc/ans.hip (``gsvc_expand_stream``); the device
+encoder csrc/ans_enc.hip (``gsvc_encode_stream``, here ``entropy_code_device``)
+restates ``entropy_code``, which stays the reference its bytes must equal.
 """
 from __future__ import annotations
 
@@ -135,6 +137,52 @@ def entropy_code(stream_v1: bytes, segment: int = 32) -> bytes:
     return out
 
 
+def coded_capacity(sizes, segment: int = 32):
+    """``gsvc_encode_stream_bytes``: (offsets [F + 1] of the frames' worst-case
+    slots in the device encoder's output, its workspace bytes) for frames of
+    ``sizes`` splats."""
+    import ctypes
+
+    from . import _lib as L
+    sizes = [int(n) for n in sizes]
+    if any(n >= 1 << 31 for n in sizes):
+        raise ValueError("a frame's splat count does not fit the header's i32")
+    counts = (ctypes.c_int * max(len(sizes), 1))(*sizes)
+    offs = (ctypes.c_longlong * (len(sizes) + 1))()
+    work = ctypes.c_size_t(0)
+    L.call("gsvc_encode_stream_bytes", len(sizes), counts, int(segment), offs, ctypes.byref(work))
+    return list(offs), int(work.value)
+
+
+def entropy_code_device(frames_v1_dev, sizes, segment: int = 32):
+    """``entropy_code`` of every frame of a list on the device
+    (``gsvc_encode_stream``, csrc/ans_enc.hip): ``frames_v1_dev`` is a uint8
+    tensor on a HIP device holding the concatenated version-1 frames (header and
+    planes each), ``sizes`` their splat counts.  One call codes the list; the
+    coded lengths are read back once.  Returns the list of coded frames, byte
+    for byte what ``entropy_code`` gives for each."""
+    import ctypes
+
+    import torch
+
+    from . import _lib as L
+    sizes = [int(n) for n in sizes]
+    if not sizes:
+        return []
+    t = frames_v1_dev
+    need = sum(HEADER_BYTES + SPLAT_BYTES * max(n, 0) for n in sizes)
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() >= need):
+        raise ValueError(f"frames_v1_dev is a contiguous uint8 tensor of at least {need} bytes on a HIP device")
+    offs, work_bytes = coded_capacity(sizes, segment)
+    out = torch.empty((offs[-1],), dtype=torch.uint8, device=t.device)
+    lengths = torch.empty((len(sizes),), dtype=torch.int64, device=t.device)
+    work = torch.empty((work_bytes,), dtype=torch.uint8, device=t.device)
+    counts = (ctypes.c_int * len(sizes))(*sizes)
+    L.call("gsvc_encode_stream", len(sizes), counts, L.ptr(t), int(segment), L.ptr(out), out.numel(),
+           L.ptr(lengths), L.ptr(work), work.numel(), L.stream(t.device))
+    return [out[o:o + n].cpu().numpy().tobytes() for o, n in zip(offs, lengths.cpu().tolist())]
+
+
 def parse_coded(buf) -> dict:
     """The fields a version-2 frame adds, checked against its length: S, n_seg,
     payload_bytes, the frequency tables and the directory.  ValueError on any
@@ -237,6 +285,7 @@ def channel_bits(stream_v2: bytes) -> dict:
                 state_bytes=4 * h["n_seg"], word_bytes=h["payload_bytes"] - 4 * h["n_seg"])
 
 
-__all__ = ["entropy_code", "entropy_expand", "parse_coded", "normalise", "channel_bits",
+__all__ = ["entropy_code", "entropy_expand", "entropy_code_device", "coded_capacity", "parse_coded",
+           "normalise", "channel_bits",
            "coded_length", "ALPHABETS", "PROB_BITS", "MAX_SEGMENT", "TABLE_BYTES",
            "STREAM_VERSION_CODED"]

@@ -248,25 +248,57 @@ def pack_planes_host(xyz, codes_chol, codes_rgb) -> bytes:
     return a + b.reshape(n * 3).tobytes()
 
 
+def _frame_parts(model):
+    """(header bytes, xyz, codes_chol, codes_rgb) of the model's quantized state."""
+    _, _, _, codes_chol, codes_rgb, _ = model.quantized(commit=False)
+    xyz = model._xyz.detach().float().contiguous()
+    uq, vq = model.cholesky_quantizer, model.features_dc_quantizer
+    head = _header(xyz.shape[0], model.H, model.W, model._delta, uq.scale.detach().cpu().tolist(),
+                   uq.beta.detach().cpu().tolist(), vq.codebooks.cpu().reshape(-1).tolist())
+    return head, xyz, codes_chol, codes_rgb
+
+
+def encode_frames(models, entropy: bool = False, segment: int = 32) -> List[bytes]:
+    """``encode_frame`` of every model of a list.  Models on one HIP device are
+    packed into one device buffer (headers uploaded, ``gsvc_pack_splats``
+    writing the planes behind them) and, with ``entropy``, coded there in one
+    ``gsvc_encode_stream`` call: the F coded lengths are read back once and each
+    frame's bytes copied out.  CPU models are packed and coded on the host
+    (``ans.entropy_code``); the bytes are the same either way."""
+    models = list(models)
+    if entropy and not 1 <= int(segment) <= ans.MAX_SEGMENT:
+        raise ValueError(f"segment = {segment}, not in 1..{ans.MAX_SEGMENT}")
+    with torch.no_grad():
+        parts = [_frame_parts(m) for m in models]
+        devices = {p[1].device for p in parts}
+        if len(devices) > 1:
+            return [encode_frames([m], entropy, segment)[0] for m in models]
+        if not parts or not parts[0][1].is_cuda:
+            v1 = [head + pack_planes_host(xyz.numpy(), cc.numpy(), cr.numpy())
+                  for head, xyz, cc, cr in parts]
+            return [ans.entropy_code(s, segment) for s in v1] if entropy else v1
+        device = parts[0][1].device
+        sizes = [p[1].shape[0] for p in parts]
+        offs = [0]
+        for n in sizes:
+            offs.append(offs[-1] + HEADER_BYTES + SPLAT_BYTES * n)
+        buf = torch.empty((offs[-1],), dtype=torch.uint8, device=device)
+        for o, (head, xyz, cc, cr) in zip(offs, parts):
+            buf[o:o + HEADER_BYTES].copy_(torch.frombuffer(bytearray(head), dtype=torch.uint8))
+            L.call("gsvc_pack_splats", xyz.shape[0], L.ptr(xyz), L.ptr(cc), L.ptr(cr),
+                   ctypes.c_void_p(buf.data_ptr() + o + HEADER_BYTES), L.stream(device))
+        if entropy:
+            return ans.entropy_code_device(buf, sizes, segment)
+        blob = buf.cpu().numpy().tobytes()
+        return [blob[a:b] for a, b in zip(offs, offs[1:])]
+
+
 def encode_frame(model, entropy: bool = False, segment: int = 32) -> bytes:
     """The model's quantized parameters as one frame stream: ``256 + 7 * N``
     bytes, or with ``entropy`` their entropy-coded transcoding in segments of
-    ``segment`` splats (``ans.entropy_code``)."""
-    with torch.no_grad():
-        _, _, _, codes_chol, codes_rgb, _ = model.quantized(commit=False)
-        xyz = model._xyz.detach().float().contiguous()
-        n = xyz.shape[0]
-        uq, vq = model.cholesky_quantizer, model.features_dc_quantizer
-        head = _header(n, model.H, model.W, model._delta, uq.scale.detach().cpu().tolist(),
-                       uq.beta.detach().cpu().tolist(), vq.codebooks.cpu().reshape(-1).tolist())
-        if xyz.is_cuda:
-            planes = torch.empty((SPLAT_BYTES * n,), dtype=torch.uint8, device=xyz.device)
-            L.call("gsvc_pack_splats", n, L.ptr(xyz), L.ptr(codes_chol), L.ptr(codes_rgb),
-                   L.ptr(planes), L.stream(xyz.device))
-            body = planes.cpu().numpy().tobytes()
-        else:
-            body = pack_planes_host(xyz.numpy(), codes_chol.numpy(), codes_rgb.numpy())
-    return ans.entropy_code(head + body, segment) if entropy else head + body
+    ``segment`` splats: ``ans.entropy_code``'s bytes, coded on the device for a
+    model on a HIP device (``encode_frames`` with one frame)."""
+    return encode_frames([model], entropy, segment)[0]
 
 
 def unpack_frames_host(streams: Sequence[bytes], cholesky_bound=(0.5, 0.0, 0.5), prev=None):
@@ -485,7 +517,8 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
     return out
 
 
-__all__ = ["GaussianVideoFrameQ", "GaussianVideoDelta", "Bits", "encode_frame", "decode_frames",
+__all__ = ["GaussianVideoFrameQ", "GaussianVideoDelta", "Bits", "encode_frame", "encode_frames",
+           "decode_frames",
            "unpack_frames", "unpack_frames_host", "pack_planes_host", "parse_header",
            "compress_video", "HEADER_BYTES", "SPLAT_BYTES", "STREAM_MAGIC", "STREAM_VERSION",
            "STREAM_VERSION_CODED", "entropy_code", "entropy_expand"]

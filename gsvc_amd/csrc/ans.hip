@@ -26,19 +26,11 @@
 // host copy cannot make it read or write out of bounds.
 #include <vector>
 
-#include "stream.h"
+#include "ans.h"
 
 namespace gsvc {
 
 constexpr int kAnsBlock = 256;
-constexpr int kAnsChannels = 7;
-constexpr int kProbBits = 12;
-constexpr int kProbOne = 1 << kProbBits;
-constexpr unsigned kRansL = 1u << 16;
-constexpr int kMaxSegment = 4096;
-constexpr int kAnsSymbols = 3 * 64 + 2 * 8 + 2 * 256;
-constexpr int kTableBytes = 2 * kAnsSymbols;
-constexpr int kCodedFixedBytes = kHeaderBytes + kTableBytes;  // what precedes the low plane
 constexpr int kExpandFrames = 32;                             // frames per launch
 constexpr int kCopyBytesPerLane = 64;                         // a version-1 frame's copy
 constexpr int kChunk = 4;                                     // splats decoded per payload window
@@ -46,13 +38,6 @@ constexpr int kChunk = 4;                                     // splats decoded 
 constexpr int kWindowLines = (14 * kChunk + 15 + 15) / 16;
 constexpr int kWindowDwords = 4 * kWindowLines;
 constexpr int kWindowStride = kWindowDwords + 1;  // odd: the lanes' windows start in distinct banks
-
-__host__ __device__ constexpr int ans_alphabet(int c) { return c < 3 ? 64 : c < 5 ? 8 : 256; }
-// symbols before channel c in the tables
-__host__ __device__ constexpr int ans_first(int c) {
-    return c < 3 ? 64 * c : c < 5 ? 192 + 8 * (c - 3) : 208 + 256 * (c - 5);
-}
-static_assert(ans_first(6) + ans_alphabet(6) == kAnsSymbols, "table layout");
 
 struct ExpandArgs {
     int nframes;
@@ -67,16 +52,6 @@ typedef unsigned short __attribute__((may_alias)) window_u16;
 // slot table entry: symbol | (f - 1) << 8 | (slot - b) << 20
 __device__ __forceinline__ unsigned slot_entry(unsigned sym, unsigned f, unsigned j) {
     return sym | (f - 1u) << 8 | j << 20;
-}
-
-// The aligned dword at q, with bytes outside [lo, hi) read as 0.
-__device__ __forceinline__ unsigned ld_dword(uintptr_t q, uintptr_t lo, uintptr_t hi) {
-    if (q >= lo && q + 4 <= hi) return *reinterpret_cast<const unsigned *>(q);
-    unsigned v = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (q + b >= lo && q + b < hi) v |= (unsigned)*reinterpret_cast<const unsigned char *>(q + b) << (8 * b);
-    return v;
 }
 
 // The aligned 16 bytes at q, with bytes outside [lo, hi) read as 0.

@@ -52,8 +52,9 @@ enum gsvc_status {
 };
 
 /* ABI version 2: gsvc_debug_set / gsvc_debug_set_ptr moved to the diagnostic
- * library (gsvc_amd_diag.h); GSVC_ERR_CAPTURE added. */
-#define GSVC_ABI_VERSION 2
+ * library (gsvc_amd_diag.h); GSVC_ERR_CAPTURE added.
+ * ABI version 3: gsvc_encode_stream_bytes / gsvc_encode_stream added. */
+#define GSVC_ABI_VERSION 3
 
 /* Library identity and error reporting. */
 int gsvc_abi_version(void);
@@ -788,6 +789,38 @@ int gsvc_unpack_stream(int num_frames, const unsigned char *stream_host,
                        const float *prev_cholesky, const float *prev_features, int prev_points,
                        float *xq, float *Lq, float *cq, float *Lpre, long long out_capacity,
                        void *workspace, size_t workspace_bytes, void *stream);
+
+/* The encoder of the version-2 stream: for every frame exactly the bytes
+ * gsvc_amd.ans.entropy_code(stream_v1, segment) gives (gsvc_amd/ans.py is the
+ * host statement both entries below mirror: its _symbols, normalise, coder and
+ * layout; DESIGN.md 13b "Encoder").  num_points [num_frames] are the frames'
+ * splat counts in host memory; everything is sized by them, never by a header
+ * in device memory.
+ *
+ * gsvc_encode_stream_bytes mirrors ans.coded_length at the worst-case payload
+ * (every symbol emits a word): coded_offsets [num_frames + 1] are the byte
+ * offsets of the frames' slots in the output buffer, each slot 256 + 1440 +
+ * 2 N + 4 (n_seg + 1) + 4 n_seg + 14 N bytes rounded up to a multiple of 4;
+ * *workspace_bytes is what gsvc_encode_stream needs.  GSVC_ERR_ARG for a
+ * segment outside 1..4096, a negative count, or a worst-case payload beyond
+ * the format's u32 offsets. */
+int gsvc_encode_stream_bytes(int num_frames, const int *num_points, int segment,
+                             long long *coded_offsets, size_t *workspace_bytes);
+
+/* Codes the num_frames concatenated version-1 frames at frames_dev (256 + 7 N
+ * bytes each, at any byte offsets) as ans.entropy_code does: frame f's coded
+ * bytes start at coded_dev + coded_offsets[f] and coded_bytes_dev[f] (device,
+ * 64-bit) receives their length; the bytes between that length and the next
+ * slot are unspecified.  Histograms, ans.normalise, the coder, the directory
+ * scan and the assembly of the frame all run on the device, in integers, up to
+ * 32 frames per launch; equal inputs give equal bytes.  The output header
+ * carries the host's N.  The workspace is 16-byte aligned.  Argument errors as
+ * above; GSVC_ERR_WORKSPACE, before any launch, when coded_capacity is below
+ * coded_offsets[num_frames] or workspace_bytes below the query's figure. */
+int gsvc_encode_stream(int num_frames, const int *num_points, const unsigned char *frames_dev,
+                       int segment, unsigned char *coded_dev, size_t coded_capacity,
+                       long long *coded_bytes_dev, void *workspace, size_t workspace_bytes,
+                       void *stream);
 
 #ifdef __cplusplus
 }
