@@ -10,13 +10,17 @@ fixture of test_gpu_parity:
 * 1920x1080 against the C oracle (oracle/oracle.c raster_forward /
   raster_backward, the restatement of the same kernels).
 
-Tolerances: image / alpha 1e-5 abs (float32, same op order); gradients
-1e-4 (float atomics in the backward); final_idx exact.
+Tolerances: image, alpha and the rasterizer's own gradients under the bars of
+tests/alpha_cases.py (4 x the C oracle's worst error against float64 on the
+scripted cases; all tighter than the 1e-5 / 1e-4 used before, which stay
+wherever they bound a small element more closely than a bar relative to the
+tensor's largest); gradients through the projection 1e-4; final_idx exact.
 """
 import numpy as np
 import pytest
 import torch
 
+from alpha_cases import assert_within_bar
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -56,14 +60,16 @@ def test_alpha_dense_golden(cuda, name):
     H, W = int(z["H"]), int(z["W"])
     assert int(z["tile_count"].min()) > 256  # every tile needs a second batch
     out, alpha, m, l, c, o = _forward_backward(z)
-    np.testing.assert_allclose(N(out), z["out_img"], rtol=1e-5, atol=1e-5)
-    np.testing.assert_allclose(N(out), z["torch_impl_out_img"], rtol=1e-5, atol=1e-5)
-    np.testing.assert_allclose(N(alpha), z["out_alpha"], rtol=1e-5, atol=1e-5)
+    assert_within_bar(N(out), z["out_img"], "image")
+    assert_within_bar(N(out), z["torch_impl_out_img"], "image")
+    assert_within_bar(N(alpha), z["out_alpha"], "T")
     scale = max(H, W) / 2
     np.testing.assert_allclose(N(m.grad), z["v_means2d"], rtol=1e-4, atol=1e-4 * scale)
     np.testing.assert_allclose(N(l.grad), z["v_L"], rtol=1e-4, atol=1e-3)
     np.testing.assert_allclose(N(c.grad), z["v_colors"], rtol=1e-4, atol=1e-4)
     np.testing.assert_allclose(N(o.grad), z["v_opacity"], rtol=1e-4, atol=1e-4)
+    assert_within_bar(N(c.grad), z["v_colors"], "v_colors")
+    assert_within_bar(N(o.grad), z["v_opacity"], "v_opacity")
     # the kernel's own stop position per pixel
     tb = _tb(H, W)
     _, Ts, idx = ops.rasterize_forward(tb, (16, 16, 1), (W, H, 1), T(z["gaussian_ids_sorted"]),
@@ -71,6 +77,7 @@ def test_alpha_dense_golden(cuda, name):
                                        T(z["colors"]), T(z["opacity"]), T(z["background"]))
     np.testing.assert_array_equal(N(idx), z["final_idx"])
     np.testing.assert_allclose(N(Ts), z["final_Ts"], rtol=1e-5, atol=1e-7)
+    assert_within_bar(N(Ts), z["final_Ts"], "T")
     reach = N(idx) - (z["final_idx"] - z["reach"])  # entry position reached in the tile
     count = z["tile_count"]
     if name.endswith("stop"):
@@ -104,8 +111,9 @@ def test_alpha_1080p_oracle(cuda, oracle, n, chol):
                                          T(colors), T(opac), T(bg))
     r_out, r_Ts, r_idx = oracle.raster_forward(tb, H, W, ref["gids_sorted"], ref["bins"], ref["xys"],
                                                ref["conics"], colors, opac, bg)
-    np.testing.assert_allclose(N(out), r_out, rtol=1e-5, atol=1e-5)
+    assert_within_bar(N(out), r_out, "image")
     np.testing.assert_allclose(N(Ts), r_Ts, rtol=1e-5, atol=1e-6)
+    assert_within_bar(N(Ts), r_Ts, "T")
     np.testing.assert_array_equal(N(idx), r_idx)
     g = np.random.default_rng(n + 1)
     v_out = g.standard_normal((H, W, 3)).astype(np.float32)
@@ -114,6 +122,7 @@ def test_alpha_1080p_oracle(cuda, oracle, n, chol):
                                Ts, idx, T(v_out), T(v_alpha))
     rv = oracle.raster_backward(tb, H, W, ref["gids_sorted"], ref["bins"], ref["xys"], ref["conics"],
                                 colors, opac, bg, r_Ts, r_idx, v_out, v_alpha)
-    for a, b in zip(v, rv):
+    for name, a, b in zip(("v_xy", "v_conic", "v_colors", "v_opacity"), v, rv):
         b = np.asarray(b, np.float32).reshape(N(a).shape)
         np.testing.assert_allclose(N(a), b, rtol=1e-4, atol=1e-4 * max(1.0, float(np.abs(b).max())))
+        assert_within_bar(N(a), b, name)
