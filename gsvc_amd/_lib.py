@@ -125,6 +125,9 @@ _SIGS = {
     "gsvc_unpack_stream": [_I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _LL, _P, _SZ, _P],
     "gsvc_encode_stream_bytes": [_I, _P, _I, _P, _P],
     "gsvc_encode_stream": [_I, _P, _P, _I, _P, _SZ, _P, _P, _SZ, _P],
+    "gsvc_quant_train_workspace_bytes": [_I],
+    "gsvc_quant_train_step": [_P],
+    "gsvc_quant_adan_step": [_P, _P, _P, _P],
 }
 # include/gsvc_amd_diag.h: the diagnostic library's extra entry points
 _DIAG_SIGS = {
@@ -153,9 +156,10 @@ _RESTYPE = {
     "gsvc_ssim_workspace_bytes": _SZ,
     "gsvc_ssim_backward_scratch_bytes": _SZ,
     "gsvc_quant_workspace_bytes": _SZ,
+    "gsvc_quant_train_workspace_bytes": _SZ,
 }
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 _libs = {}       # path -> loaded CDLL
 _active = None   # the library ops call (load())

@@ -9,7 +9,11 @@ through a learned 6-bit uniform quantizer, colours through a 2-stage residual
 VQ -- and a non-key frame is a delta on the previous frame's parameters.  The
 quantization itself is one kernel each way (``quantize.quantize_params``); the
 render and its backward are the existing operators, the optimizer the existing
-``Adan``.
+``Adan``.  ``train_iter_quantize_fused`` is the same iteration as ONE C call
+(``gsvc_quant_train_step``, csrc/quant_train.hip): the quantizer forward, the
+fused step's render / loss / backward, the quantizer's backward, Adan on all
+five parameters and the codebooks' moving average, with the model's ``Adan``
+object still the owner of the state, so the two methods interleave freely.
 
 ``encode_frame`` writes a model as the fixed-length stream of
 include/gsvc_amd.h (256-byte header + 7 bytes per splat) or, with
@@ -34,6 +38,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import ans
+from . import train as T
 from .adan import Adan
 from .frame import loss_fn
 from .project_gaussians_2d import project_gaussians_2d
@@ -54,6 +59,142 @@ FLAG_DELTA = 1
 # unit_bit entry of one parameter group: the bits the packed stream writes, and
 # an estimate of what an entropy coder would (None in training mode)
 Bits = namedtuple("Bits", ["fixed", "entropy_estimate"])
+
+
+class _QuantStepArgs(ctypes.Structure):
+    """include/gsvc_amd.h gsvc_quant_train_args."""
+    _fields_ = [("num_points", ctypes.c_int), ("xyz", ctypes.c_void_p),
+                ("cholesky", ctypes.c_void_p), ("features", ctypes.c_void_p),
+                ("scale", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("codebooks", ctypes.c_void_p), ("cluster_size", ctypes.c_void_p),
+                ("embed_avg", ctypes.c_void_p), ("cholesky_bound", ctypes.c_void_p),
+                ("p_xyz", ctypes.c_void_p), ("p_cholesky", ctypes.c_void_p),
+                ("p_features", ctypes.c_void_p), ("background", ctypes.c_void_p),
+                ("gt", ctypes.c_void_p), ("img_height", ctypes.c_uint), ("img_width", ctypes.c_uint),
+                ("loss_kind", ctypes.c_int), ("frame_index", ctypes.c_int),
+                ("adan_state", ctypes.c_void_p), ("adan_hparams", ctypes.c_void_p),
+                ("flags", ctypes.c_int), ("decay", ctypes.c_double), ("eps", ctypes.c_double),
+                ("commitment_weight", ctypes.c_double), ("loss", ctypes.c_void_p),
+                ("render_out", ctypes.c_void_p), ("grads_out", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+                ("train_workspace", ctypes.c_void_p), ("train_workspace_bytes", ctypes.c_size_t),
+                ("det_workspace", ctypes.c_void_p), ("det_workspace_bytes", ctypes.c_size_t),
+                ("det_capacity", ctypes.c_longlong), ("stream", ctypes.c_void_p)]
+
+
+_data_ptr = torch.Tensor.data_ptr
+
+
+class BoundQuantStep:
+    """``gsvc_quant_train_step`` bound to a model's tensors (parameters, the
+    quantizers' tables, the previous frame's buffers, the 20 Adan state
+    tensors): the argument struct, the step's workspace and the four host
+    loss words are made once; a call sets the target, the frame parity, the
+    hyper-parameters, flags and stream (``train.BoundStep`` is the model).  The
+    owner rebuilds it when a bound tensor object or storage changes."""
+
+    def __init__(self, params, tables, bound, prev, background, H, W, loss_type, vq, state):
+        xyz, chol, feat, scale, beta = params
+        n = xyz.shape[0]
+        self.tensors = (*params, *tables, bound, *(prev or ()), background, *state)
+        self.ids = tuple(map(id, self.tensors))
+        self.ptrs = list(map(_data_ptr, self.tensors))
+        self.n, self.H, self.W, self.dev = n, int(H), int(W), xyz.device
+        self.state = (ctypes.c_void_p * 20)()
+        numels = [2 * n, 3 * n, 3 * n, 3, 3]
+        for k, t in enumerate(state):
+            self.state[k] = T._f32_ptr(t, "adan_state", numels[k // 4])
+        self.hp = (ctypes.c_double * 10)()
+        self.lib = L.load()
+        self.ws = torch.empty((int(self.lib.gsvc_quant_train_workspace_bytes(n)),), dtype=torch.uint8,
+                              device=self.dev)
+        self.host = self.lib.gsvc_host_alloc(16)
+        if not self.host:
+            raise RuntimeError(self.lib.gsvc_last_error().decode(errors="replace"))
+        self.host_f = (ctypes.c_float * 4).from_address(self.host)
+        a = self.args = _QuantStepArgs()
+        a.num_points = n
+        a.xyz, a.cholesky = T._f32_ptr(xyz, "_xyz", 2 * n), T._f32_ptr(chol, "_cholesky", 3 * n)
+        a.features = T._f32_ptr(feat, "_features_dc", 3 * n)
+        a.scale, a.beta = T._f32_ptr(scale, "scale", 3), T._f32_ptr(beta, "beta", 3)
+        a.codebooks = T._f32_ptr(tables[0], "codebooks", 48)
+        a.cluster_size = T._f32_ptr(tables[1], "cluster_size", 16)
+        a.embed_avg = T._f32_ptr(tables[2], "embed_avg", 48)
+        a.cholesky_bound = T._f32_ptr(bound, "cholesky_bound", 3)
+        if prev is not None:
+            a.p_xyz = T._f32_ptr(prev[0], "p_xyz", 2 * n)
+            a.p_cholesky = T._f32_ptr(prev[1], "p_cholesky", 3 * n)
+            a.p_features = T._f32_ptr(prev[2], "p_features_dc", 3 * n)
+        a.background = T._f32_ptr(background, "background", 3)
+        a.img_height, a.img_width = self.H, self.W
+        a.loss_kind = T.LOSS_KIND[loss_type]
+        a.adan_state = ctypes.addressof(self.state)
+        a.adan_hparams = ctypes.addressof(self.hp)
+        a.decay, a.eps, a.commitment_weight = vq.decay, vq.eps, vq.commitment_weight
+        self.vq_scalars = (vq.decay, vq.eps, vq.commitment_weight)
+        a.loss = self.host
+        a.workspace, a.workspace_bytes = self.ws.data_ptr(), self.ws.numel()
+        self.args_ref = ctypes.byref(a)
+        self.fn = self.lib.gsvc_quant_train_step
+
+    def __del__(self):
+        if getattr(self, "host", None):
+            try:
+                self.lib.gsvc_host_free(self.host)
+            except Exception:  # interpreter shutdown
+                pass
+            self.host = None
+
+    def __deepcopy__(self, memo):
+        return None  # a copied model binds its own tensors on its first step
+
+    def matches(self, tensors, vq) -> bool:
+        return (tuple(map(id, tensors)) == self.ids and list(map(_data_ptr, tensors)) == self.ptrs
+                and (vq.decay, vq.eps, vq.commitment_weight) == self.vq_scalars)
+
+    def step(self, gt, hparams, flags, render_out=None, grads_out=None, sync=True):
+        """One call and one read-back: (mse, mae, commitment sum 0, 1).
+        ``sync=False`` (tools' timing) only enqueues the call and returns None."""
+        if not (gt.is_cuda and gt.dtype is torch.float32 and gt.is_contiguous()
+                and gt.numel() == 3 * self.H * self.W):
+            raise RuntimeError("gt must be a contiguous float32 CUDA tensor of 3*H*W elements")
+        a = self.args
+        for k, x in enumerate(hparams):
+            self.hp[k] = x
+        # train.py's workspace of this stream: zeroed counters, the frame parity
+        ws = T._workspace(self.dev, self.n, self.H, self.W)
+        if ws.pending is not None:  # a bound step's work enqueued ahead: not for this call
+            ws.dirty = True
+            ws = T._workspace(self.dev, self.n, self.H, self.W)
+        if torch.are_deterministic_algorithms_enabled():
+            buf, cap = ws.det_workspace(self.dev, self.n, 16 * self.n)
+            a.det_workspace, a.det_workspace_bytes, a.det_capacity = buf.data_ptr(), buf.numel(), cap
+            flags |= T.TRAIN_DETERMINISTIC
+        else:
+            a.det_workspace, a.det_workspace_bytes, a.det_capacity = None, 0, 0
+        a.gt = gt.data_ptr()
+        a.frame_index = ws.frame
+        a.flags = flags
+        a.render_out = T._f32_ptr(render_out, "render_out", 3 * self.H * self.W) or None
+        a.grads_out = T._f32_ptr(grads_out, "grads_out", 8 * self.n + 6) or None
+        a.train_workspace, a.train_workspace_bytes = ws.buf_ptr, ws.buf.numel()
+        stream = T._raw_stream(self.dev.index)
+        a.stream = stream
+        T._note_launch(a.xyz)
+        rc = self.fn(self.args_ref)
+        if rc != 0:
+            ws.dirty = True
+            msg = self.lib.gsvc_last_error().decode(errors="replace")
+            raise RuntimeError(f"gsvc_quant_train_step failed (status {rc}): {msg}")
+        ws.frame += 1
+        if not sync:
+            return None
+        rc = self.lib.gsvc_stream_sync(stream)  # the reference's PSNR .item()
+        if rc != 0:
+            ws.dirty = True
+            msg = self.lib.gsvc_last_error().decode(errors="replace")
+            raise RuntimeError(f"gsvc_quant_train_step failed (status {rc}): {msg}")
+        return tuple(self.host_f)
 
 
 class _QuantFrame(nn.Module):
@@ -190,6 +331,110 @@ class _QuantFrame(nn.Module):
         self.optimizer.step()
         self.optimizer.zero_grad(set_to_none=True)
         self.scheduler.step()
+        return loss, psnr
+
+    def _fused_tensors(self, gt_image):
+        """The checks of ``train_iter_quantize_fused``; raises with the reason,
+        before anything has changed.  Returns the five parameters."""
+        if not self.quantize:
+            raise RuntimeError("train_iter_quantize_fused: the model was built with quantize=False")
+        if self.loss_type not in T.LOSS_KIND:
+            raise ValueError("train_iter_quantize_fused supports the L2 and L1 losses, not "
+                             f"{self.loss_type!r}")
+        opt = self.optimizer
+        if not isinstance(opt, Adan):
+            raise ValueError("train_iter_quantize_fused needs the Adan optimizer (opt_type='adan'), "
+                             f"not {type(opt).__name__}")
+        if self.BLOCK_H != 16 or self.BLOCK_W != 16:
+            raise ValueError("train_iter_quantize_fused needs 16x16 blocks, not "
+                             f"{self.BLOCK_H}x{self.BLOCK_W}")
+        uq = self.cholesky_quantizer
+        params = (self._xyz, self._cholesky, self._features_dc, uq.scale, uq.beta)
+        if not self._xyz.is_cuda:
+            raise RuntimeError("train_iter_quantize_fused: the model is on the CPU; the fused step "
+                               "runs on a HIP device only (train_iter_quantize runs anywhere)")
+        if opt.defaults["max_grad_norm"] > 0:
+            raise ValueError("train_iter_quantize_fused does not clip gradients (max_grad_norm > 0)")
+        group = opt.param_groups[0]["params"] if len(opt.param_groups) == 1 else ()
+        if len(group) != 5 or {id(p) for p in group} != {id(p) for p in params}:
+            raise RuntimeError("train_iter_quantize_fused: the optimizer must hold the model's five "
+                               "parameters in one group")
+        for p in params:
+            if p.grad is not None:
+                raise RuntimeError("train_iter_quantize_fused: a parameter has a pending gradient "
+                                   "(zero_grad(set_to_none=True) first)")
+            if (not p.requires_grad or p.dtype is not torch.float32 or not p.is_contiguous()
+                    or p.device != self._xyz.device):
+                raise RuntimeError("train_iter_quantize_fused: parameters must be trainable "
+                                   "contiguous float32 tensors on one device")
+        if gt_image.numel() != 3 * self.H * self.W or gt_image.device != self._xyz.device:
+            raise ValueError(f"train_iter_quantize_fused: the target must hold 3 x {self.H} x {self.W} "
+                             "elements on the model's device")
+        return params
+
+    def _fused_step(self, gt_image, render_out=None, grads_out=None):
+        """One ``gsvc_quant_train_step`` with this optimizer's state, step
+        counter and learning rate: its four loss words.  With ``grads_out``
+        (the test hook) nothing is updated and no counter moves."""
+        params = self._fused_tensors(gt_image)
+        vq, opt = self.features_dc_quantizer, self.optimizer
+        if not vq.is_initted():
+            vq.init_codebooks(self._features_dc)
+        hook = grads_out is not None
+        group = opt.param_groups[0]
+        step = group.get("step", 0) + 1
+        b1, b2, b3 = group["betas"]
+        hparams = [b1, b2, b3, 1.0 - b1 ** step, 1.0 - b2 ** step, math.sqrt(1.0 - b3 ** step),
+                   group["lr"], group["weight_decay"], group["eps"], 1.0]
+        flags = 1 if group["no_prox"] else 0
+        state = []
+        for q, p in enumerate(params):
+            if hook:  # nothing is read or written: any valid pointers
+                state += [p] * 4
+                continue
+            st = opt.state[p]
+            for k in ("exp_avg", "exp_avg_sq", "exp_avg_diff"):  # as Adan.step creates them
+                if k not in st:
+                    st[k] = torch.zeros_like(p)
+            if "neg_pre_grad" not in st or step == 1:
+                if "neg_pre_grad" not in st:
+                    st["neg_pre_grad"] = torch.zeros_like(p)
+                flags |= 1 << (1 + q)  # the kernel starts it at -grad
+            state += [st["exp_avg"], st["exp_avg_sq"], st["exp_avg_diff"], st["neg_pre_grad"]]
+        gt = gt_image.detach() if gt_image.requires_grad else gt_image
+        if gt.dtype is not torch.float32 or not gt.is_contiguous():
+            gt = gt.float().contiguous()
+        tables = (vq.codebooks, vq.cluster_size, vq.embed_avg)
+        bound = (*params, *tables, self.cholesky_bound, *(self._prev() or ()), self.background, *state)
+        bs = self.__dict__.get("_bound_quant_step")
+        if bs is None or bs.loss_kind != T.LOSS_KIND[self.loss_type] or not bs.matches(bound, vq):
+            bs = BoundQuantStep(params, tables, self.cholesky_bound, self._prev(), self.background,
+                                self.H, self.W, self.loss_type, vq, state)
+            bs.loss_kind = T.LOSS_KIND[self.loss_type]
+            self.__dict__["_bound_quant_step"] = bs
+        if not hook:
+            group["step"] = step
+            T.bump_param_epoch()  # work another fused step enqueued ahead is stale now
+        return bs.step(gt, hparams, flags, render_out, grads_out)
+
+    def train_iter_quantize_fused(self, gt_image):
+        """``train_iter_quantize`` as one C call (``gsvc_quant_train_step``):
+        returns (loss, psnr), the loss a host scalar tensor.  The model's Adan
+        object keeps the state, the step counter and the learning rate, and the
+        scheduler steps, so this and ``train_iter_quantize`` interleave at any
+        iteration.  HIP devices, Adan, 16x16 blocks and the L2 / L1 losses only:
+        anything else raises (nothing falls back to the op-by-op method)."""
+        mse, mae, s0, s1 = self._fused_step(gt_image)
+        opt = self.optimizer
+        opt._opt_called = True  # the step ran: keeps StepLR's call-order check quiet
+        self.scheduler.optimizer._opt_called = True
+        self.scheduler.step()
+        vq = self.features_dc_quantizer
+        n = self._xyz.shape[0]
+        loss = torch.empty(())
+        loss.numpy()[...] = ((mae if self.loss_type == "L1" else mse)
+                             + vq.commitment_weight * (s0 + s1) / (3 * n))
+        psnr = 10 * math.log10(1.0 / mse)
         return loss, psnr
 
 
@@ -438,7 +683,7 @@ def _load_overfit(model, cur: dict, prev: Optional[dict]) -> None:
 def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: Sequence[int] = (1,),
                    iterations: int = 30000, lr: float = 1e-3, device="cuda:0", loss_type="L2",
                    delta_base: str = "overfit", seed: Optional[int] = None, entropy: bool = False,
-                   segment: int = 32) -> dict:
+                   segment: int = 32, fused: bool = False) -> dict:
     """Fine-tune every overfit frame model of ``state_dict`` (``frame_<i>`` ->
     {_xyz, _cholesky, _features_dc}, i from 1) under quantization against
     ``frames`` ([1,3,H,W] each) and encode it: frames listed in ``K_frames``
@@ -455,7 +700,9 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
     Returns {"streams", "psnr", "bpp" (fixed-length), "bpp_entropy_estimate",
     "state_dicts"}; the best-PSNR state of each frame is kept, as the reference
     does.  With ``entropy`` the streams are entropy-coded (version 2, segments
-    of ``segment`` splats) and "bpp_coded" gives their ``8 * len / (H * W)``."""
+    of ``segment`` splats) and "bpp_coded" gives their ``8 * len / (H * W)``.
+    ``fused`` runs every iteration as ``train_iter_quantize_fused`` (one C call;
+    HIP devices and the L2 / L1 losses only -- anything else raises)."""
     if delta_base not in ("overfit", "decoded"):
         raise ValueError("delta_base is 'overfit' or 'decoded'")
     if seed is not None:
@@ -483,8 +730,9 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
         model._init_data()
         model.train()
         best_psnr, best_sd = -math.inf, None
+        train_iter = model.train_iter_quantize_fused if fused else model.train_iter_quantize
         for _ in range(int(iterations)):
-            _, psnr = model.train_iter_quantize(gt)
+            _, psnr = train_iter(gt)
             if psnr > best_psnr:
                 best_psnr, best_sd = psnr, copy.deepcopy(model.state_dict())
         if best_sd is not None:

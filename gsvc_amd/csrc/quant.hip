@@ -21,107 +21,12 @@
 // kQuantMaxBlocks blocks strides over N), a wave folds by xor-shuffles 32..1,
 // lane 0..K-1 of the block adds the 4 wave sums in order and stores the block
 // partial, and a second one-block launch adds the partials in block order.
-#include "stream.h"
+#include "quant_dev.h"
 
 namespace gsvc {
 
-constexpr int kQuantBlock = 256;
-constexpr int kQuantMaxBlocks = 1024;
-constexpr int kQuantSums = 8;  // floats per block partial (6 used by the backward, 2 by the forward)
-constexpr int kQMax = 63;      // 6-bit codes
-constexpr int kCodewords = 8, kStages = 2;
-
-// stream layout: stream.h
+// stream layout: stream.h; the shared device functions: quant_dev.h
 static_assert(kOffCodebooks + 4 * 3 * kStages * kCodewords <= kHeaderBytes, "header layout");
-
-static int quant_blocks(int n) { return n < 1 ? 1 : std::min(ceil_div(n, kQuantBlock), kQuantMaxBlocks); }
-
-struct f3 {
-    float x, y, z;
-};
-
-__device__ __forceinline__ f3 load3(const float *p, long long i) {
-    return *reinterpret_cast<const f3 *>(p + 3 * i);
-}
-__device__ __forceinline__ void store3(float *p, long long i, float a, float b, float c) {
-    f3 v{a, b, c};
-    *reinterpret_cast<f3 *>(p + 3 * i) = v;
-}
-
-// The decoder's arithmetic: half bits / codes / codewords -> xq, Lq, cq and the
-// pre-bound Cholesky entries (what a following delta frame adds).
-struct Recon {
-    float xq[2], Lq[3], Lpre[3], cq[3];
-};
-
-__device__ __forceinline__ Recon reconstruct(_Float16 h0, _Float16 h1, const int code[3],
-                                             const float scale[3], const float beta[3],
-                                             const float bound[3], const float e0[3],
-                                             const float e1[3], bool delta, const float px[2],
-                                             const float pL[3], const float pc[3]) {
-    Recon r;
-    r.xq[0] = (float)h0;
-    r.xq[1] = (float)h1;
-    if (delta) {
-        r.xq[0] = r.xq[0] + px[0];
-        r.xq[1] = r.xq[1] + px[1];
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float deq = __fadd_rn(__fmul_rn((float)code[k], scale[k]), beta[k]);
-        const float lb = deq + bound[k];
-        r.Lq[k] = delta ? lb + pL[k] : lb;
-        r.Lpre[k] = delta ? deq + pL[k] : deq;
-        const float c = e0[k] + e1[k];
-        r.cq[k] = delta ? c + pc[k] : c;
-    }
-    return r;
-}
-
-__device__ __forceinline__ float quant_raw(float c, float scale, float beta) {
-    return __fdiv_rn(c - beta, scale);
-}
-__device__ __forceinline__ float quant_code(float raw) {
-    return rintf(fminf(fmaxf(raw, 0.0f), (float)kQMax));
-}
-
-// nearest codeword of one stage: index (lowest of equal distances), distance
-__device__ __forceinline__ int vq_nearest(const float r[3], const float *__restrict__ cb,
-                                          float &dmin) {
-    int best = 0;
-    float bd = 0.0f;
-#pragma unroll
-    for (int j = 0; j < kCodewords; ++j) {
-        const float a = r[0] - cb[3 * j], b = r[1] - cb[3 * j + 1], c = r[2] - cb[3 * j + 2];
-        const float d = (a * a + b * b) + c * c;
-        if (j == 0 || d < bd) {
-            bd = d;
-            best = j;
-        }
-    }
-    dmin = bd;
-    return best;
-}
-
-// Block partial of K per-lane sums -> partials[block * kQuantSums + k].
-template <int K>
-__device__ __forceinline__ void block_partial(float (&v)[K], float *__restrict__ partials) {
-    __shared__ float wave_sums[kQuantBlock / 64][K];
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[k] = v[k] + __shfl_xor(v[k], m, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) wave_sums[wave][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < K) {
-        float s = wave_sums[0][threadIdx.x];
-        for (int w = 1; w < kQuantBlock / 64; ++w) s = s + wave_sums[w][threadIdx.x];
-        partials[blockIdx.x * kQuantSums + threadIdx.x] = s;
-    }
-}
 
 // out_a[0..na) and out_b[0..nb) = the partials' columns summed in block order
 __global__ __launch_bounds__(64) void quant_combine_kernel(const float *__restrict__ partials,
@@ -129,8 +34,7 @@ __global__ __launch_bounds__(64) void quant_combine_kernel(const float *__restri
                                                            float *out_b, int nb) {
     const int k = threadIdx.x;
     if (k >= na + nb) return;
-    float s = partials[k];
-    for (int b = 1; b < nblocks; ++b) s = s + partials[b * kQuantSums + k];
+    const float s = sum_block_order(partials + k, nblocks, kQuantSums);
     if (k < na)
         out_a[k] = s;
     else
@@ -210,33 +114,17 @@ __global__ __launch_bounds__(kQuantBlock) void quant_backward_kernel(
          i += (long long)gridDim.x * kQuantBlock) {
         *reinterpret_cast<float2 *>(v_xyz + 2 * i) = *reinterpret_cast<const float2 *>(v_xq + 2 * i);
         const f3 c = load3(chol, i), vl = load3(v_Lq, i), vq = load3(v_cq, i);
-        const float cv[3] = {c.x, c.y, c.z}, vL[3] = {vl.x, vl.y, vl.z};
-        float vch[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float raw = quant_raw(cv[k], scale[k], beta[k]);
-            const float q = quant_code(raw);
-            const float mask = (raw >= 0.0f && raw <= (float)kQMax) ? 1.0f : 0.0f;
-            vch[k] = vL[k] * mask;
-            sums[k] = sums[k] + vL[k] * (q - mask * raw);
-            sums[3 + k] = sums[3 + k] + vL[k] * (1.0f - mask);
-        }
-        store3(v_chol, i, vch[0], vch[1], vch[2]);
-        // each stage is straight-through on its own residual: d cq / d f = 2
-        float g[3] = {2.0f * vq.x, 2.0f * vq.y, 2.0f * vq.z};
+        const float cv[3] = {c.x, c.y, c.z}, vL[3] = {vl.x, vl.y, vl.z}, vc[3] = {vq.x, vq.y, vq.z};
+        float fv[3] = {0.0f, 0.0f, 0.0f};
+        int i0 = 0, i1 = 0;
         if (commit) {
             const f3 f = load3(feat, i);
-            const int i0 = codes_rgb[2 * i] & (kCodewords - 1), i1 = codes_rgb[2 * i + 1] & (kCodewords - 1);
-            const float fv[3] = {f.x, f.y, f.z};
-            const float *cb1 = cb + 3 * kCodewords;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float r1 = fv[k] - cb[3 * i0 + k];  // stage 0: r0 - e0, also stage 1's residual
-                const float t0 = vc0 * (2.0f * r1);
-                const float t1 = vc1 * (2.0f * (r1 - cb1[3 * i1 + k]));
-                g[k] = g[k] + (t0 + t1);
-            }
+            fv[0] = f.x, fv[1] = f.y, fv[2] = f.z;
+            i0 = codes_rgb[2 * i] & (kCodewords - 1), i1 = codes_rgb[2 * i + 1] & (kCodewords - 1);
         }
+        float vch[3], g[3];
+        quant_backward_splat(cv, vL, vc, scale, beta, commit, fv, cb, i0, i1, vc0, vc1, vch, g, sums);
+        store3(v_chol, i, vch[0], vch[1], vch[2]);
         store3(v_feat, i, g[0], g[1], g[2]);
     }
     block_partial(sums, partials);
@@ -342,6 +230,26 @@ __global__ __launch_bounds__(kQuantBlock) void unpack_kernel(
     }
 }
 
+// the forward's training variant and its combine (quant_dev.h)
+int launch_quant_forward_train(const char *what, int num_points, const float *xyz,
+                               const float *cholesky, const float *features, const float *scale,
+                               const float *beta, const float *codebooks,
+                               const float *cholesky_bound, const float *p_xyz,
+                               const float *p_cholesky, const float *p_features, float *xq,
+                               float *Lq, float *cq, unsigned char *codes_chol,
+                               unsigned char *codes_rgb, float *partials, float *commit_sums,
+                               hipStream_t s) {
+    const int blocks = quant_blocks(num_points);
+    hipLaunchKernelGGL(quant_forward_kernel<true>, dim3(blocks), dim3(kQuantBlock), 0, s, num_points,
+                       xyz, cholesky, features, scale, beta, codebooks, cholesky_bound, p_xyz,
+                       p_cholesky, p_features, xq, Lq, cq, codes_chol, codes_rgb, partials);
+    int rc = check_launch(what);
+    if (rc) return rc;
+    hipLaunchKernelGGL(quant_combine_kernel, dim3(1), dim3(64), 0, s, (const float *)partials,
+                       blocks, commit_sums, 2, (float *)nullptr, 0);
+    return check_launch(what);
+}
+
 // the walk's launch, for gsvc_unpack_splats and gsvc_unpack_stream (stream.h)
 int launch_unpack_walk(const char *what, int num_frames, const unsigned char *stream_dev,
                        long long total_bytes, long long total_splats, long long nmax,
@@ -386,17 +294,11 @@ extern "C" int gsvc_quant_params_forward(
         if (commit_sums) return dev_zero(commit_sums, 2 * sizeof(float), s);
         return GSVC_OK;
     }
-    if (commit_sums) {
-        float *partials = (float *)workspace;
-        hipLaunchKernelGGL(quant_forward_kernel<true>, dim3(blocks), dim3(kQuantBlock), 0, s, num_points,
-                           xyz, cholesky, features, scale, beta, codebooks, cholesky_bound, p_xyz,
-                           p_cholesky, p_features, xq, Lq, cq, codes_chol, codes_rgb, partials);
-        int rc = check_launch("quant_params_forward");
-        if (rc) return rc;
-        hipLaunchKernelGGL(quant_combine_kernel, dim3(1), dim3(64), 0, s, (const float *)partials,
-                           blocks, commit_sums, 2, (float *)nullptr, 0);
-        return check_launch("quant_params_forward (combine)");
-    }
+    if (commit_sums)
+        return launch_quant_forward_train("quant_params_forward", num_points, xyz, cholesky, features,
+                                          scale, beta, codebooks, cholesky_bound, p_xyz, p_cholesky,
+                                          p_features, xq, Lq, cq, codes_chol, codes_rgb,
+                                          (float *)workspace, commit_sums, s);
     hipLaunchKernelGGL(quant_forward_kernel<false>, dim3(blocks), dim3(kQuantBlock), 0, s, num_points,
                        xyz, cholesky, features, scale, beta, codebooks, cholesky_bound, p_xyz,
                        p_cholesky, p_features, xq, Lq, cq, codes_chol, codes_rgb, (float *)nullptr);

@@ -53,8 +53,10 @@ enum gsvc_status {
 
 /* ABI version 2: gsvc_debug_set / gsvc_debug_set_ptr moved to the diagnostic
  * library (gsvc_amd_diag.h); GSVC_ERR_CAPTURE added.
- * ABI version 3: gsvc_encode_stream_bytes / gsvc_encode_stream added. */
-#define GSVC_ABI_VERSION 3
+ * ABI version 3: gsvc_encode_stream_bytes / gsvc_encode_stream added.
+ * ABI version 4: gsvc_quant_train_workspace_bytes / gsvc_quant_train_step /
+ * gsvc_quant_adan_step added. */
+#define GSVC_ABI_VERSION 4
 
 /* Library identity and error reporting. */
 int gsvc_abi_version(void);
@@ -821,6 +823,88 @@ int gsvc_encode_stream(int num_frames, const int *num_points, const unsigned cha
                        int segment, unsigned char *coded_dev, size_t coded_capacity,
                        long long *coded_bytes_dev, void *workspace, size_t workspace_bytes,
                        void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Fused quantized training step of the compression stage: one
+ * train_iter_quantize (GaussianSplats_Compress.py:86-98, 181-193) with the L2
+ * or L1 loss and Adan, one call, no host sync, no allocation.  On ``stream``
+ * it enqueues, in order:
+ *   1. the quantizer forward (gsvc_quant_params_forward's kernel with its
+ *      commitment sums) into xq, Lq, cq and the code buffers of ``workspace``;
+ *   2. gsvc_train_step_sum_args in gradients-only mode on (xq, Lq, cq): tanh,
+ *      projection, binning, forward, clamp, loss, backward; no cholesky_bound
+ *      (Lq holds it), no rgb_w; its gradient records [N,9] go to the
+ *      workspace, the image bits of gsvc_render_frame_sum to render_out;
+ *   3. the per-splat kernel: gsvc_quant_params_backward's op sequence with
+ *      v_commit[0] = v_commit[1] = (float)(commitment_weight / (3 N)) and the
+ *      PRE-step codebooks, the Adan update (gsvc_adan_step's op sequence) of
+ *      xyz, cholesky and features in place, block partials of v_scale, v_beta
+ *      (gsvc_quant_params_backward's reduction: the same bits) and of the
+ *      codebooks' member counts and sums -- stage 0: the features f under
+ *      i0, stage 1: f - e0 (pre-step e0) under i1, both from the PRE-update
+ *      features, as ResidualVQ8.ema_update sees them in the forward; these
+ *      are added in double: each wave's 64 members in splat order, pass after
+ *      pass of the grid's stride loop, then the block's four waves in order;
+ *   4. a one-workgroup kernel: the partials in block order (the member sums
+ *      in double, rounded to float once), the Adan update of scale and beta,
+ *      and per stage, with the float decay d and 1 - d,
+ *        cluster_size = fma(1 - d, counts, cluster_size * d)   (embed_avg alike)
+ *        total = sum of cluster_size in index order
+ *        smoothed = (cluster_size + eps) / (total + 8 eps) * total
+ *        codebooks = embed_avg / smoothed
+ *      and loss[0..3] = {mean squared error, mean absolute error, commitment
+ *      sum of stage 0, of stage 1} (device or pinned host memory; read it
+ *      after gsvc_stream_sync).  The step's loss is loss[loss_kind] +
+ *      commitment_weight * (loss[2] + loss[3]) / (3 N).
+ * No float atomics anywhere in 1, 3 and 4: equal inputs give equal bits (step
+ * 2 with GSVC_TRAIN_DETERMINISTIC in ``flags``, which needs det_workspace).
+ * adan_state: host array of 20 device pointers, per parameter (xyz, cholesky,
+ * features, scale, beta) its {exp_avg, exp_avg_sq, exp_avg_diff,
+ * neg_pre_grad}; adan_hparams: the ten of gsvc_train_step_sum.  flags: bit 0
+ * no_prox; bit 1 + q: parameter q takes its first step;
+ * GSVC_TRAIN_DETERMINISTIC.  p_xyz, p_cholesky, p_features: all three (a delta
+ * frame) or all NULL.  train_workspace (gsvc_train_step_workspace_bytes,
+ * zeroed and with frame_index's parity as for gsvc_train_step_sum) and
+ * det_workspace belong to step 2.  grads_out (test hook, [8 N + 6]): when
+ * non-NULL nothing is updated -- no parameter, state or codebook byte -- and
+ * the gradients go there: v_xyz [N,2], v_cholesky [N,3], v_features [N,3],
+ * v_scale [3], v_beta [3].  Everything is validated before the first launch;
+ * num_points < 1 is an argument error; a capturing stream is refused
+ * (GSVC_ERR_CAPTURE) as by gsvc_train_step_sum.  Not part of the reference. */
+typedef struct gsvc_quant_train_args {
+    int num_points;
+    float *xyz, *cholesky, *features;             /* [N,2], [N,3], [N,3] */
+    float *scale, *beta;                          /* [3] each */
+    float *codebooks, *cluster_size, *embed_avg;  /* [2,8,3], [2,8], [2,8,3] */
+    const float *cholesky_bound;                  /* [3] */
+    const float *p_xyz, *p_cholesky, *p_features;
+    const float *background, *gt;
+    unsigned img_height, img_width;
+    int loss_kind, frame_index;
+    float *const *adan_state;
+    const double *adan_hparams;
+    int flags;
+    double decay, eps, commitment_weight;
+    float *loss, *render_out, *grads_out;
+    void *workspace;
+    size_t workspace_bytes;
+    void *train_workspace;
+    size_t train_workspace_bytes;
+    void *det_workspace;
+    size_t det_workspace_bytes;
+    long long det_capacity;
+    void *stream;
+} gsvc_quant_train_args;
+size_t gsvc_quant_train_workspace_bytes(int num_points);
+int gsvc_quant_train_step(const gsvc_quant_train_args *args);
+/* Steps 3 and 4 alone, on caller-given gradient records (grad_records [N,9] =
+ * {d_xq 2, d_Lq 3, d_cq 3, unused}) and codes_rgb [N,2] (the forward's): the
+ * render fields of ``args`` (background, gt, sizes, loss_kind, frame_index,
+ * render_out, train / det workspace) are not read; ``loss`` is optional and
+ * receives {0, 0, commit_sums[0], commit_sums[1]} (commit_sums optional,
+ * device memory; zeros without). */
+int gsvc_quant_adan_step(const gsvc_quant_train_args *args, const float *grad_records,
+                         const unsigned char *codes_rgb, const float *commit_sums);
 
 #ifdef __cplusplus
 }
