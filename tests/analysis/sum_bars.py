@@ -1,0 +1,72 @@
+"""Where the bars of tests/sum_cases.py come from: two float32 restatements
+against the float64 references of tests/sum_cases.py over every case -- the C
+oracle (forward.cu:512-627 / backward.cu:696-862 / foward2d.cu / backward2d.cu
+in float32, sums in double) and sum_cases.chain_np in float32 with every sum
+taken sequentially in float32 in pixel order (the least favourable honest
+summation: it covers the kernels' DPP trees and float atomics).  Worst error
+per quantity: image and losses absolute (losses also relative), each gradient
+relative to the reference's largest element -- the worst of the whole tensor,
+the edge subset and, on the counts cases, each tile's own splats.  The
+kernels' bar is 4 times the worse of the two figures.
+
+    python tests/analysis/sum_bars.py
+"""
+import os
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+for p in (os.path.dirname(HERE), os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle")):
+    sys.path.insert(0, p)
+
+import sum_cases as S  # noqa: E402
+
+OP_KEYS = ("image",) + S.OP_GRADS
+FUSED_KEYS = ("render", "loss_abs", "loss_rel") + tuple(n for n, _ in S.PARAM_GRADS)
+
+
+def measure():
+    """{restatement: {quantity: (worst, case)}} over every case."""
+    worst = {w: {} for w in ("oracle", "float32-seq")}
+
+    def note(who, key, val, cid):
+        if val > worst[who].get(key, (-1.0, ""))[0]:
+            worst[who][key] = (val, cid)
+
+    for cid in S.OP_IDS:
+        c = S.op_case(cid)
+        line = f"{cid:14s} op    nudged {c['nudged']:2d}"
+        for who, run in (("oracle", S.oracle_op), ("float32-seq", S.float32_op)):
+            e = S.op_errors(cid, *run(c))
+            assert e["idx"] == 0, (cid, who)
+            for k in OP_KEYS:
+                note(who, k, S.worst_of(e, k), cid)
+            line += f" | {who} " + " ".join(f"{S.worst_of(e, k):8.2e}" for k in OP_KEYS)
+        print(line)
+    for cid in S.FUSED_IDS:
+        p, r = S.fused_case(cid)
+        line = f"{cid:14s} fused nudged {p['nudged']:2d}"
+        for who, run in (("oracle", S.oracle_fused), ("float32-seq", S.float32_fused)):
+            e = S.fused_errors(cid, *run(p))
+            for k in FUSED_KEYS:
+                note(who, k, S.worst_of(e, k), cid)
+            line += f" | {who} " + " ".join(f"{S.worst_of(e, k):8.2e}" for k in FUSED_KEYS)
+        print(line)
+    return worst
+
+
+def main():
+    t0 = time.time()
+    worst = measure()
+    print(f"\n{time.time() - t0:.1f} s")
+    keys = list(dict.fromkeys(OP_KEYS + FUSED_KEYS))
+    print(f"{'':12s} {'oracle':>10s} {'case':14s} {'float32-seq':>11s} {'case':14s} {'bar':>10s}")
+    for k in keys:
+        (a, ca), (b, cb) = worst["oracle"][k], worst["float32-seq"][k]
+        print(f"{k:12s} {a:10.2e} {ca:14s} {b:11.2e} {cb:14s} {4 * max(a, b):10.2e}")
+    print("WORST = dict(" + ", ".join(
+        f"{k}={max(worst['oracle'][k][0], worst['float32-seq'][k][0]):.2e}" for k in keys) + ")")
+
+
+if __name__ == "__main__":
+    main()
