@@ -65,4 +65,39 @@ __device__ __forceinline__ float adan_update(const AdanScalars &S, float p, floa
     return p;
 }
 
+// One splat's rows of the four state tensors state[] = {exp_avg, exp_avg_sq,
+// exp_avg_diff, neg_pre_grad} of a [N, C] parameter (C = 1, 2, 3), one vector
+// access per row.  Load, step and store are separate calls, so a kernel issues
+// every load before its first arithmetic and every store after its last update.
+template <int C>
+struct AdanRows {
+    float m[C] = {}, v[C] = {}, df[C] = {}, npg[C] = {};
+};
+template <int C>
+__device__ __forceinline__ void adan_rows_load(AdanRows<C> &R, float *const (&state)[4], long long i) {
+    ld_row<C>(state[0], i, R.m);
+    ld_row<C>(state[1], i, R.v);
+    ld_row<C>(state[2], i, R.df);
+    ld_row<C>(state[3], i, R.npg);
+}
+// p[0..C) updated in place from the gradients g[0..C); first: the parameter's
+// first step (the loaded neg_pre_grad is ignored)
+template <int C>
+__device__ __forceinline__ void adan_rows_step(const AdanScalars &S, int first, AdanRows<C> &R,
+                                               float *p, const float *g) {
+#pragma unroll
+    for (int e = 0; e < C; ++e) {
+        if (first) R.npg[e] = -(g[e] * S.clip);
+        p[e] = adan_update(S, p[e], g[e], R.m[e], R.v[e], R.df[e], R.npg[e]);
+    }
+}
+template <int C>
+__device__ __forceinline__ void adan_rows_store(float *const (&state)[4], long long i,
+                                                const AdanRows<C> &R) {
+    st_row<C>(state[0], i, R.m);
+    st_row<C>(state[1], i, R.v);
+    st_row<C>(state[2], i, R.df);
+    st_row<C>(state[3], i, R.npg);
+}
+
 }  // namespace gsvc

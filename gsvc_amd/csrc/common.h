@@ -156,4 +156,37 @@ __device__ __forceinline__ float exp_neg(float s) {
 
 __host__ __device__ __forceinline__ int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// Row i of a [N, C] float tensor (C = 1, 2, 3) as one vector access (a row of
+// 2 or 3 floats is one dwordx2 / x3).
+struct Row3 {
+    float x, y, z;
+};
+template <int C>
+__device__ __forceinline__ void ld_row(const float *base, long long i, float *out) {
+    const float *p = base + C * i;
+    if constexpr (C == 2) {
+        const float2 t = *reinterpret_cast<const float2 *>(p);
+        out[0] = t.x;
+        out[1] = t.y;
+    } else if constexpr (C == 3) {
+        const Row3 t = *reinterpret_cast<const Row3 *>(p);
+        out[0] = t.x;
+        out[1] = t.y;
+        out[2] = t.z;
+    } else {
+        out[0] = p[0];
+    }
+}
+template <int C>
+__device__ __forceinline__ void st_row(float *base, long long i, const float *in) {
+    float *p = base + C * i;
+    if constexpr (C == 2) {
+        *reinterpret_cast<float2 *>(p) = make_float2(in[0], in[1]);
+    } else if constexpr (C == 3) {
+        *reinterpret_cast<Row3 *>(p) = Row3{in[0], in[1], in[2]};
+    } else {
+        p[0] = in[0];
+    }
+}
+
 }  // namespace gsvc

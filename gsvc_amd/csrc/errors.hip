@@ -86,8 +86,7 @@ extern "C" int gsvc_debug_set(int key, int value) {
         case GSVC_KNOB_TILE_WG256: case GSVC_KNOB_TILE_ABLATE: case GSVC_KNOB_TILE_NO_GROUPS:
         case GSVC_KNOB_GROUP_MIN: case GSVC_KNOB_NO_SIGMA_CUT: case GSVC_KNOB_RECORD_SLABS:
         case GSVC_KNOB_BATCH_ID_SLABS: case GSVC_KNOB_KEEP_ORDER: case GSVC_KNOB_ALPHA_BWD_ABLATE:
-        case GSVC_KNOB_SPLAT_ONE_LANE: case GSVC_KNOB_SPARSE_ABLATE: case GSVC_KNOB_GENERIC_RENDER:
-        case GSVC_KNOB_RENDER_STAMPS:
+        case GSVC_KNOB_SPARSE_ABLATE: case GSVC_KNOB_GENERIC_RENDER: case GSVC_KNOB_RENDER_STAMPS:
             break;
         default:
             return -1;

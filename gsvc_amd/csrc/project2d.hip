@@ -33,8 +33,7 @@ __global__ __launch_bounds__(256) void project2d_fwd_kernel(
     num_tiles_hit[i] = hit;
 }
 
-// backward2d.cu:8-51; cov2d_to_conic_vjp (helpers.cuh:71-82) expanded in glm's
-// column-major mat2 product order: V = ((-X) * G) * X.
+// backward2d.cu:8-51 (project2d.h project2d_vjp).
 __global__ __launch_bounds__(256) void project2d_bwd_kernel(
     int n, const float *__restrict__ L, float hw, float hh,
     const int *__restrict__ radii, const float *__restrict__ conics,
@@ -42,38 +41,22 @@ __global__ __launch_bounds__(256) void project2d_bwd_kernel(
     float *__restrict__ v_cov2d, float2 *__restrict__ v_mean2d, float *__restrict__ v_L) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float g11 = 0.0f, g12 = 0.0f, g22 = 0.0f, vl0 = 0.0f, vl1 = 0.0f, vl2 = 0.0f;
+    float g[3] = {0.0f, 0.0f, 0.0f}, vl[3] = {0.0f, 0.0f, 0.0f};
     float2 vm = make_float2(0.0f, 0.0f);
     if (radii[i] > 0) {
-        const float X00 = conics[3 * i], X01 = conics[3 * i + 1], X10 = X01, X11 = conics[3 * i + 2];
         const float *vc = v_conic + (size_t)sc * i;  // row i (row stride sc floats)
-        const float G00 = vc[0], G01 = vc[1], G10 = G01, G11 = vc[2];
-        const float N00 = -X00, N01 = -X01, N10 = -X10, N11 = -X11;
-        const float P00 = N00 * G00 + N10 * G01;
-        const float P01 = N01 * G00 + N11 * G01;
-        const float P10 = N00 * G10 + N10 * G11;
-        const float P11 = N01 * G10 + N11 * G11;
-        const float V00 = P00 * X00 + P10 * X01;
-        const float V01 = P01 * X00 + P11 * X01;
-        const float V10 = P00 * X10 + P10 * X11;
-        const float V11 = P01 * X10 + P11 * X11;
-        g11 = V00;
-        g12 = V10 + V01;
-        g22 = V11;
-        const float l11 = L[3 * i], l21 = L[3 * i + 1], l22 = L[3 * i + 2];
-        vl0 = 2.0f * l11 * g11 + 2.0f * g12 * l21;  // doubled cross term: backward2d.cu:39
-        vl1 = 2.0f * l11 * g12 + 2.0f * l21 * g22;
-        vl2 = 2.0f * l22 * g22;
+        project2d_vjp(conics[3 * i], conics[3 * i + 1], conics[3 * i + 2], vc[0], vc[1], vc[2],
+                      L[3 * i], L[3 * i + 1], L[3 * i + 2], g, vl);
         const float *vx = v_xy + (size_t)sxy * i;
         vm = make_float2(vx[0] * hw, vx[1] * hh);
     }
-    v_cov2d[3 * i] = g11;
-    v_cov2d[3 * i + 1] = g12;
-    v_cov2d[3 * i + 2] = g22;
+    v_cov2d[3 * i] = g[0];
+    v_cov2d[3 * i + 1] = g[1];
+    v_cov2d[3 * i + 2] = g[2];
     v_mean2d[i] = vm;
-    v_L[3 * i] = vl0;
-    v_L[3 * i + 1] = vl1;
-    v_L[3 * i + 2] = vl2;
+    v_L[3 * i] = vl[0];
+    v_L[3 * i + 1] = vl[1];
+    v_L[3 * i + 2] = vl[2];
 }
 
 // bindings.cu:21-39 (degenerate covariances give zeros here; the reference

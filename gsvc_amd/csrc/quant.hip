@@ -57,14 +57,14 @@ __global__ __launch_bounds__(kQuantBlock) void quant_forward_kernel(
     float sums[2] = {0.0f, 0.0f};
     for (long long i = (long long)blockIdx.x * kQuantBlock + threadIdx.x; i < n;
          i += (long long)gridDim.x * kQuantBlock) {
-        const float2 x = *reinterpret_cast<const float2 *>(xyz + 2 * i);
-        const f3 c = load3(chol, i), f = load3(feat, i);
-        const _Float16 h0 = (_Float16)x.x, h1 = (_Float16)x.y;
-        const float cv[3] = {c.x, c.y, c.z};
+        float x[2], cv[3], r0[3];
+        ld_row<2>(xyz, i, x);
+        ld_row<3>(chol, i, cv);
+        ld_row<3>(feat, i, r0);
+        const _Float16 h0 = (_Float16)x[0], h1 = (_Float16)x[1];
         int code[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) code[k] = (int)quant_code(quant_raw(cv[k], scale[k], beta[k]));
-        const float r0[3] = {f.x, f.y, f.z};
         float d0, d1;
         const int i0 = vq_nearest(r0, cb, d0);
         const float e0[3] = {cb[3 * i0], cb[3 * i0 + 1], cb[3 * i0 + 2]};
@@ -74,16 +74,14 @@ __global__ __launch_bounds__(kQuantBlock) void quant_forward_kernel(
         const float e1[3] = {cb1[3 * i1], cb1[3 * i1 + 1], cb1[3 * i1 + 2]};
         float px[2] = {0.0f, 0.0f}, pL[3] = {0.0f, 0.0f, 0.0f}, pc[3] = {0.0f, 0.0f, 0.0f};
         if (delta) {
-            const float2 a = *reinterpret_cast<const float2 *>(p_xyz + 2 * i);
-            const f3 b = load3(p_chol, i), g = load3(p_feat, i);
-            px[0] = a.x, px[1] = a.y;
-            pL[0] = b.x, pL[1] = b.y, pL[2] = b.z;
-            pc[0] = g.x, pc[1] = g.y, pc[2] = g.z;
+            ld_row<2>(p_xyz, i, px);
+            ld_row<3>(p_chol, i, pL);
+            ld_row<3>(p_feat, i, pc);
         }
         const Recon r = reconstruct(h0, h1, code, scale, beta, bound, e0, e1, delta, px, pL, pc);
-        *reinterpret_cast<float2 *>(xq + 2 * i) = make_float2(r.xq[0], r.xq[1]);
-        store3(Lq, i, r.Lq[0], r.Lq[1], r.Lq[2]);
-        store3(cq, i, r.cq[0], r.cq[1], r.cq[2]);
+        st_row<2>(xq, i, r.xq);
+        st_row<3>(Lq, i, r.Lq);
+        st_row<3>(cq, i, r.cq);
         codes_chol[3 * i] = (unsigned char)code[0];
         codes_chol[3 * i + 1] = (unsigned char)code[1];
         codes_chol[3 * i + 2] = (unsigned char)code[2];
@@ -112,20 +110,22 @@ __global__ __launch_bounds__(kQuantBlock) void quant_backward_kernel(
     float sums[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // v_scale[3], v_beta[3]
     for (long long i = (long long)blockIdx.x * kQuantBlock + threadIdx.x; i < n;
          i += (long long)gridDim.x * kQuantBlock) {
-        *reinterpret_cast<float2 *>(v_xyz + 2 * i) = *reinterpret_cast<const float2 *>(v_xq + 2 * i);
-        const f3 c = load3(chol, i), vl = load3(v_Lq, i), vq = load3(v_cq, i);
-        const float cv[3] = {c.x, c.y, c.z}, vL[3] = {vl.x, vl.y, vl.z}, vc[3] = {vq.x, vq.y, vq.z};
+        float vx[2], cv[3], vL[3], vc[3];
+        ld_row<2>(v_xq, i, vx);
+        st_row<2>(v_xyz, i, vx);
+        ld_row<3>(chol, i, cv);
+        ld_row<3>(v_Lq, i, vL);
+        ld_row<3>(v_cq, i, vc);
         float fv[3] = {0.0f, 0.0f, 0.0f};
         int i0 = 0, i1 = 0;
         if (commit) {
-            const f3 f = load3(feat, i);
-            fv[0] = f.x, fv[1] = f.y, fv[2] = f.z;
+            ld_row<3>(feat, i, fv);
             i0 = codes_rgb[2 * i] & (kCodewords - 1), i1 = codes_rgb[2 * i + 1] & (kCodewords - 1);
         }
         float vch[3], g[3];
         quant_backward_splat(cv, vL, vc, scale, beta, commit, fv, cb, i0, i1, vc0, vc1, vch, g, sums);
-        store3(v_chol, i, vch[0], vch[1], vch[2]);
-        store3(v_feat, i, g[0], g[1], g[2]);
+        st_row<3>(v_chol, i, vch);
+        st_row<3>(v_feat, i, g);
     }
     block_partial(sums, partials);
 }
@@ -137,8 +137,9 @@ __global__ __launch_bounds__(kQuantBlock) void pack_kernel(
     const unsigned char *__restrict__ codes_rgb, unsigned char *__restrict__ planes) {
     const long long i = (long long)blockIdx.x * kQuantBlock + threadIdx.x;
     if (i >= n) return;
-    const float2 x = *reinterpret_cast<const float2 *>(xyz + 2 * i);
-    const _Float16 h0 = (_Float16)x.x, h1 = (_Float16)x.y;
+    float x[2];
+    ld_row<2>(xyz, i, x);
+    const _Float16 h0 = (_Float16)x[0], h1 = (_Float16)x[1];
     unsigned short b0, b1;
     __builtin_memcpy(&b0, &h0, 2);
     __builtin_memcpy(&b1, &h1, 2);
@@ -216,10 +217,10 @@ __global__ __launch_bounds__(kQuantBlock) void unpack_kernel(
             const float e1[3] = {rd_f32(cb1), rd_f32(cb1 + 4), rd_f32(cb1 + 8)};
             const Recon r = reconstruct(h0, h1, code, scale, beta, bound, e0, e1, delta, px, pL, pc);
             const long long o = so + i;
-            *reinterpret_cast<float2 *>(xq + 2 * o) = make_float2(r.xq[0], r.xq[1]);
-            store3(Lq, o, r.Lq[0], r.Lq[1], r.Lq[2]);
-            store3(cq, o, r.cq[0], r.cq[1], r.cq[2]);
-            if (Lpre) store3(Lpre, o, r.Lpre[0], r.Lpre[1], r.Lpre[2]);
+            st_row<2>(xq, o, r.xq);
+            st_row<3>(Lq, o, r.Lq);
+            st_row<3>(cq, o, r.cq);
+            if (Lpre) st_row<3>(Lpre, o, r.Lpre);
             px[0] = r.xq[0], px[1] = r.xq[1];
 #pragma unroll
             for (int k = 0; k < 3; ++k) pL[k] = r.Lpre[k], pc[k] = r.cq[k];

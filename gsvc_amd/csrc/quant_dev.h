@@ -18,18 +18,6 @@ constexpr int kCodewords = 8, kStages = 2;
 
 inline int quant_blocks(int n) { return n < 1 ? 1 : std::min(ceil_div(n, kQuantBlock), kQuantMaxBlocks); }
 
-struct f3 {
-    float x, y, z;
-};
-
-__device__ __forceinline__ f3 load3(const float *p, long long i) {
-    return *reinterpret_cast<const f3 *>(p + 3 * i);
-}
-__device__ __forceinline__ void store3(float *p, long long i, float a, float b, float c) {
-    f3 v{a, b, c};
-    *reinterpret_cast<f3 *>(p + 3 * i) = v;
-}
-
 // The decoder's arithmetic: half bits / codes / codewords -> xq, Lq, cq and the
 // pre-bound Cholesky entries (what a following delta frame adds).
 struct Recon {

@@ -55,24 +55,6 @@ struct QuantTrainSplatArgs {
     double *epart;     // [blocks, kEmaValues]
 };
 
-template <int C>
-__device__ __forceinline__ void row_ld(const float *base, long long i, float *out) {
-    if constexpr (C == 2) {
-        const float2 t = *reinterpret_cast<const float2 *>(base + 2 * i);
-        out[0] = t.x, out[1] = t.y;
-    } else {
-        const f3 t = load3(base, i);
-        out[0] = t.x, out[1] = t.y, out[2] = t.z;
-    }
-}
-template <int C>
-__device__ __forceinline__ void row_st(float *base, long long i, const float *in) {
-    if constexpr (C == 2)
-        *reinterpret_cast<float2 *>(base + 2 * i) = make_float2(in[0], in[1]);
-    else
-        store3(base, i, in[0], in[1], in[2]);
-}
-
 __global__ __launch_bounds__(kQuantBlock) void quant_train_splat_kernel(QuantTrainSplatArgs A) {
     __shared__ int s_code[kQuantBlock];          // i0 | i1 << 3; -1: no splat
     __shared__ float s_val[6][kMemberRow];       // f (3), f - e0 (3)
@@ -94,29 +76,20 @@ __global__ __launch_bounds__(kQuantBlock) void quant_train_splat_kernel(QuantTra
         float fv[3] = {0.0f, 0.0f, 0.0f}, r1[3] = {0.0f, 0.0f, 0.0f};
         if (i < A.n) {
             // every operand up front: one round trip per lane
-            float p[8], rec[8], m[8], v[8], df[8], npg[8];
-            row_ld<2>(A.xyz, i, p);
-            row_ld<3>(A.chol, i, p + 2);
-            row_ld<3>(A.feat, i, p + 5);
+            float p[8], rec[8];
+            ld_row<2>(A.xyz, i, p);
+            ld_row<3>(A.chol, i, p + 2);
+            ld_row<3>(A.feat, i, p + 5);
 #pragma unroll
             for (int e = 0; e < 8; ++e) rec[e] = A.rec[9 * i + e];
             const int i0 = A.codes_rgb[2 * i] & (kCodewords - 1);
             const int i1 = A.codes_rgb[2 * i + 1] & (kCodewords - 1);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) m[e] = v[e] = df[e] = npg[e] = 0.0f;
+            AdanRows<2> sx;
+            AdanRows<3> sc, sf;
             if (upd) {
-                row_ld<2>(A.state[0][0], i, m);
-                row_ld<2>(A.state[0][1], i, v);
-                row_ld<2>(A.state[0][2], i, df);
-                row_ld<2>(A.state[0][3], i, npg);
-                row_ld<3>(A.state[1][0], i, m + 2);
-                row_ld<3>(A.state[1][1], i, v + 2);
-                row_ld<3>(A.state[1][2], i, df + 2);
-                row_ld<3>(A.state[1][3], i, npg + 2);
-                row_ld<3>(A.state[2][0], i, m + 5);
-                row_ld<3>(A.state[2][1], i, v + 5);
-                row_ld<3>(A.state[2][2], i, df + 5);
-                row_ld<3>(A.state[2][3], i, npg + 5);
+                adan_rows_load(sx, A.state[0], i);
+                adan_rows_load(sc, A.state[1], i);
+                adan_rows_load(sf, A.state[2], i);
             }
             fv[0] = p[5], fv[1] = p[6], fv[2] = p[7];
             code = i0 | (i1 << 3);
@@ -129,32 +102,19 @@ __global__ __launch_bounds__(kQuantBlock) void quant_train_splat_kernel(QuantTra
             quant_backward_splat(p + 2, rec + 2, rec + 5, scale, beta, true, fv, A.cb, i0, i1, A.vc,
                                  A.vc, g + 2, g + 5, sums);
             if (upd) {
-                float pnew[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const int q = e < 2 ? 0 : (e < 5 ? 1 : 2);
-                    if (A.first[q]) npg[e] = -(g[e] * A.S.clip);
-                    pnew[e] = adan_update(A.S, p[e], g[e], m[e], v[e], df[e], npg[e]);
-                }
-                row_st<2>(A.xyz, i, pnew);
-                row_st<2>(A.state[0][0], i, m);
-                row_st<2>(A.state[0][1], i, v);
-                row_st<2>(A.state[0][2], i, df);
-                row_st<2>(A.state[0][3], i, npg);
-                row_st<3>(A.chol, i, pnew + 2);
-                row_st<3>(A.state[1][0], i, m + 2);
-                row_st<3>(A.state[1][1], i, v + 2);
-                row_st<3>(A.state[1][2], i, df + 2);
-                row_st<3>(A.state[1][3], i, npg + 2);
-                row_st<3>(A.feat, i, pnew + 5);
-                row_st<3>(A.state[2][0], i, m + 5);
-                row_st<3>(A.state[2][1], i, v + 5);
-                row_st<3>(A.state[2][2], i, df + 5);
-                row_st<3>(A.state[2][3], i, npg + 5);
+                adan_rows_step(A.S, A.first[0], sx, p, g);
+                adan_rows_step(A.S, A.first[1], sc, p + 2, g + 2);
+                adan_rows_step(A.S, A.first[2], sf, p + 5, g + 5);
+                st_row<2>(A.xyz, i, p);
+                adan_rows_store(A.state[0], i, sx);
+                st_row<3>(A.chol, i, p + 2);
+                adan_rows_store(A.state[1], i, sc);
+                st_row<3>(A.feat, i, p + 5);
+                adan_rows_store(A.state[2], i, sf);
             } else {
-                row_st<2>(A.grads_out, i, g);
-                row_st<3>(A.grads_out + 2 * (size_t)A.n, i, g + 2);
-                row_st<3>(A.grads_out + 5 * (size_t)A.n, i, g + 5);
+                st_row<2>(A.grads_out, i, g);
+                st_row<3>(A.grads_out + 2 * (size_t)A.n, i, g + 2);
+                st_row<3>(A.grads_out + 5 * (size_t)A.n, i, g + 5);
             }
         }
         if (upd) {  // (uniform over the grid)

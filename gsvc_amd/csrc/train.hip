@@ -21,10 +21,11 @@
 //       of the tile into the splats' gradient records (one atomic request per
 //       (splat, tile)).  Image, final_idx and v_out never reach HBM: per pixel
 //       the step reads gt once;
-//   train_splat_kernel  one lane per splat: projection VJP (the reference's
-//       doubled L cross term), activation VJPs and the Adan update of every
-//       parameter element; an extra first workgroup sums the tiles' errors in
-//       a fixed order into the loss.
+//   train_splat_kernel  two waves per 64 splats, a geometry and a colour
+//       half: projection VJP (the reference's doubled L cross term),
+//       activation VJPs and the Adan update of every parameter element; an
+//       extra first workgroup sums the tiles' errors in a fixed order into
+//       the loss.
 #include <type_traits>
 
 #include "adan.h"
@@ -1401,7 +1402,6 @@ struct TrainSplatArgs {
     int *cids;
     int *m_next;
     long long *stamps;  // diagnostic: int64[waves][8]
-    int split;          // two waves per 64 splats (splat_step_split); 0: one lane per splat
 };
 
 // GSVC_TRAIN_CARRY: splat i's projection for the next frame from its updated
@@ -1458,41 +1458,10 @@ __device__ __forceinline__ int carry_splat(const TrainSplatArgs &A, int i, const
     return (int)((x1 - x0) * (y1 - y0));
 }
 
-// Row i of a [N, C] float tensor (C = 1, 2, 3) as one vector access.
-struct Row3 {
-    float x, y, z;
-};
-template <int C>
-__device__ __forceinline__ void ld_row(const float *base, int i, float *out) {
-    const float *p = base + (size_t)C * (size_t)i;
-    if constexpr (C == 2) {
-        const float2 t = *reinterpret_cast<const float2 *>(p);
-        out[0] = t.x;
-        out[1] = t.y;
-    } else if constexpr (C == 3) {
-        const Row3 t = *reinterpret_cast<const Row3 *>(p);
-        out[0] = t.x;
-        out[1] = t.y;
-        out[2] = t.z;
-    } else {
-        out[0] = p[0];
-    }
-}
-template <int C>
-__device__ __forceinline__ void st_row(float *base, int i, const float *in) {
-    float *p = base + (size_t)C * (size_t)i;
-    if constexpr (C == 2) {
-        *reinterpret_cast<float2 *>(p) = make_float2(in[0], in[1]);
-    } else if constexpr (C == 3) {
-        *reinterpret_cast<Row3 *>(p) = Row3{in[0], in[1], in[2]};
-    } else {
-        p[0] = in[0];
-    }
-}
-
 // Diagnostic (GSVC_KNOB_STAMP = 4 with gsvc_debug_set_ptr): s_memrealtime
 // stamps per wave by lane 0 -- start, operands landed, Adan stores issued,
-// carry done, M added, stores acknowledged -- as int64[8] at st.
+// carry done (a colour wave: the barrier passed), M stored, stores
+// acknowledged -- as int64[8] at st, two waves per 64 splats.
 __device__ __forceinline__ void splat_stamp(long long *st, int k) {
     if (st) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1501,162 +1470,21 @@ __device__ __forceinline__ void splat_stamp(long long *st, int k) {
     }
 }
 
-// One splat's step: the projection VJP, activation VJPs and the Adan update of
-// its elements (update == 0: the gradients into grads_out).  st: stamps
-// (kStamp instances only).
+// The splats' step: the projection VJP, activation VJPs and the Adan update of
+// every parameter element (update == 0: the gradients into grads_out), over
+// two waves per 64 splats (256-thread workgroups: 128 splats, waves 0 / 2
+// their geometry halves, 1 / 3 their colour halves): the colour wave loads
+// the colour gradient, the features, rgb_W and their Adan rows, updates them
+// and hands the new values over LDS; the geometry wave does the projection
+// VJP, the xyz / cholesky Adan elements and, after the barrier, the carry (it
+// needs all nine new values).  Each wave loads every operand up front, before
+// any arithmetic: one round trip per lane (rec is written for every splat by
+// the projection, so its load needs no radius test; a first step's
+// neg_pre_grad is loaded and ignored).  One lane per splat had half the waves
+// with twice the loads and Adan work each (782 one-wave latency chains on 1024
+// SIMDs were the kernel).  st: the wave's stamps (kStamp only).
 template <bool kStamp>
-__device__ __forceinline__ int splat_step(const TrainSplatArgs &A, int i, long long *st) {
-    // Every operand is loaded up front, before any arithmetic: one round trip
-    // per lane instead of three (gradient + radius -> record -> Adan state).
-    // rec is written for every splat by the projection, so its load needs no
-    // radius test; a first step's neg_pre_grad is loaded and ignored.
-    float4 g0 = A.grad[4 * i];      // v_xy.x, v_xy.y, v_conic 0, v_conic 1
-    float4 g1 = A.grad[4 * i + 1];  // v_conic 2, v_colors r g b
-    if (A.det_off) {
-        // the splat's (splat, tile) partials in bbox row-major order, then the
-        // overflow atomics (zero unless det_cap was too small)
-        const long long b = A.det_off[i], e = min((long long)A.det_off[i + 1], A.det_cap);
-        float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-        for (long long k = b; k < e; ++k) {
-            const float4 p0 = A.det_part[2 * k], p1 = A.det_part[2 * k + 1];
-            s0.x += p0.x; s0.y += p0.y; s0.z += p0.z; s0.w += p0.w;
-            s1.x += p1.x; s1.y += p1.y; s1.z += p1.z; s1.w += p1.w;
-        }
-        g0 = make_float4(s0.x + g0.x, s0.y + g0.y, s0.z + g0.z, s0.w + g0.w);
-        g1 = make_float4(s1.x + g1.x, s1.y + g1.y, s1.z + g1.z, s1.w + g1.w);
-    }
-    const float4 r0 = A.rec[3 * i], r2 = A.rec[3 * i + 2];
-    const int rad = A.radii[i];
-    const float c0 = A.chol[3 * i], c1 = A.chol[3 * i + 1], c2 = A.chol[3 * i + 2];
-    const float x0 = A.xyz[2 * i], x1 = A.xyz[2 * i + 1];
-    const float f0 = A.feat[3 * i], f1 = A.feat[3 * i + 1], f2 = A.feat[3 * i + 2];
-    const float w = A.rgbw ? A.rgbw[i] : 1.0f;
-    // the carry's hull, with the other operands (not a round trip after the update)
-    const uint2 hull = A.carry ? A.chull[i] : make_uint2(0u, 0u);
-    if (kStamp) splat_stamp(st, 1);
-    const bool upd = A.update != 0;
-    // Adan state rows, one vector access per (tensor, splat): xyz e 0-1, cholesky
-    // 2-4, features 5-7, rgb_W 8 (a row of 2 or 3 floats is one dwordx2 / x3)
-    float m[9], v[9], df[9], npg[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) m[e] = v[e] = df[e] = npg[e] = 0.0f;
-    if (upd) {
-        ld_row<2>(A.state[0][0], i, m);
-        ld_row<2>(A.state[0][1], i, v);
-        ld_row<2>(A.state[0][2], i, df);
-        ld_row<2>(A.state[0][3], i, npg);
-        ld_row<3>(A.state[1][0], i, m + 2);
-        ld_row<3>(A.state[1][1], i, v + 2);
-        ld_row<3>(A.state[1][2], i, df + 2);
-        ld_row<3>(A.state[1][3], i, npg + 2);
-        ld_row<3>(A.state[2][0], i, m + 5);
-        ld_row<3>(A.state[2][1], i, v + 5);
-        ld_row<3>(A.state[2][2], i, df + 5);
-        ld_row<3>(A.state[2][3], i, npg + 5);
-        if (A.rgbw_train) {
-            ld_row<1>(A.state[3][0], i, m + 8);
-            ld_row<1>(A.state[3][1], i, v + 8);
-            ld_row<1>(A.state[3][2], i, df + 8);
-            ld_row<1>(A.state[3][3], i, npg + 8);
-        }
-    }
-    // 2D projection VJP, backward2d.cu:8-51 (the op's project2d_bwd_kernel sequence)
-    float vl0 = 0.f, vl1 = 0.f, vl2 = 0.f, vmx = 0.f, vmy = 0.f;
-    float l11 = c0, l21 = c1, l22 = c2;
-    if (A.chol_bound) {
-        l11 = l11 + A.chol_bound[0];
-        l21 = l21 + A.chol_bound[1];
-        l22 = l22 + A.chol_bound[2];
-    }
-    if (rad > 0) {
-        const float X00 = r2.z, X01 = r0.w, X10 = X01, X11 = r2.w;
-        const float G00 = g0.z, G01 = g0.w, G10 = G01, G11 = g1.x;
-        const float N00 = -X00, N01 = -X01, N10 = -X10, N11 = -X11;
-        const float P00 = N00 * G00 + N10 * G01;
-        const float P01 = N01 * G00 + N11 * G01;
-        const float P10 = N00 * G10 + N10 * G11;
-        const float P11 = N01 * G10 + N11 * G11;
-        const float V00 = P00 * X00 + P10 * X01;
-        const float V01 = P01 * X00 + P11 * X01;
-        const float V10 = P00 * X10 + P10 * X11;
-        const float V11 = P01 * X10 + P11 * X11;
-        const float g11 = V00, g12 = V10 + V01, g22 = V11;
-        vl0 = 2.0f * l11 * g11 + 2.0f * g12 * l21;  // doubled cross term: backward2d.cu:39
-        vl1 = 2.0f * l11 * g12 + 2.0f * l21 * g22;
-        vl2 = 2.0f * l22 * g22;
-        vmx = g0.x * A.hw;
-        vmy = g0.y * A.hh;
-    }
-    // activations (GaussianSplats_Represent.py:57-70): tanh, + bound, * rgb_W
-    const float t0 = tanhf(x0), t1 = tanhf(x1);
-    const float dx0 = vmx * (1.0f - t0 * t0), dx1 = vmy * (1.0f - t1 * t1);
-    const float df0 = g1.y * w, df1 = g1.z * w, df2 = g1.w * w;
-    const float dw = (g1.y * f0 + g1.z * f1) + g1.w * f2;
-    if (!upd) {
-        float *o = A.grads_out + 9 * (size_t)i;
-        o[0] = dx0;
-        o[1] = dx1;
-        o[2] = vl0;
-        o[3] = vl1;
-        o[4] = vl2;
-        o[5] = df0;
-        o[6] = df1;
-        o[7] = df2;
-        o[8] = A.rgbw_train ? dw : 0.0f;
-        return 0;
-    }
-    // Adan on the 8 (9 with rgb_W) elements of this splat
-    const float g[9] = {dx0, dx1, vl0, vl1, vl2, df0, df1, df2, dw};
-    const float pin[9] = {x0, x1, c0, c1, c2, f0, f1, f2, w};
-    float pnew[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) {
-        const int q = e < 2 ? 0 : (e < 5 ? 1 : (e < 8 ? 2 : 3));
-        pnew[e] = pin[e];
-        if (q == 3 && !A.rgbw_train) continue;
-        if (A.first[q]) npg[e] = -(g[e] * A.S.clip);
-        pnew[e] = adan_update(A.S, pin[e], g[e], m[e], v[e], df[e], npg[e]);
-    }
-    // the rows back, one vector store per (tensor, splat)
-    st_row<2>(A.xyz, i, pnew);
-    st_row<2>(A.state[0][0], i, m);
-    st_row<2>(A.state[0][1], i, v);
-    st_row<2>(A.state[0][2], i, df);
-    st_row<2>(A.state[0][3], i, npg);
-    st_row<3>(A.chol, i, pnew + 2);
-    st_row<3>(A.state[1][0], i, m + 2);
-    st_row<3>(A.state[1][1], i, v + 2);
-    st_row<3>(A.state[1][2], i, df + 2);
-    st_row<3>(A.state[1][3], i, npg + 2);
-    st_row<3>(A.feat, i, pnew + 5);
-    st_row<3>(A.state[2][0], i, m + 5);
-    st_row<3>(A.state[2][1], i, v + 5);
-    st_row<3>(A.state[2][2], i, df + 5);
-    st_row<3>(A.state[2][3], i, npg + 5);
-    if (A.rgbw_train) {
-        st_row<1>(A.rgbw, i, pnew + 8);
-        st_row<1>(A.state[3][0], i, m + 8);
-        st_row<1>(A.state[3][1], i, v + 8);
-        st_row<1>(A.state[3][2], i, df + 8);
-        st_row<1>(A.state[3][3], i, npg + 8);
-    }
-    if (kStamp) splat_stamp(st, 2);
-    const int hits = A.carry ? carry_splat(A, i, pnew, hull) : 0;
-    if (kStamp) splat_stamp(st, 3);
-    return hits;
-}
-
-// splat_step over two waves per 64 splats (256-thread workgroups: 128
-// splats, waves 0 / 2 their geometry halves, 1 / 3 their colour halves): the
-// colour wave loads the colour gradient, the features, rgb_W and their Adan
-// rows, updates them and hands the new values over LDS; the geometry wave
-// does the projection VJP, the xyz / cholesky Adan elements and, after the
-// barrier, the carry (it needs all nine new values).  The same op sequence
-// per element as splat_step, so the same bits; twice the waves, each with
-// about half the loads and Adan work (782 one-wave latency chains on 1024
-// SIMDs were the kernel).  The deterministic mode's partial sums
-// are split the same way (each half its components, in splat_step's order).
-__device__ __forceinline__ int splat_step_split(const TrainSplatArgs &A, int base) {
+__device__ __forceinline__ int splat_step(const TrainSplatArgs &A, int base, long long *st) {
     __shared__ float s_cp[2][4][64];  // per splat group: new feature r g b, rgb_W
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, grp = w >> 1;
     const int i = base + grp * 64 + lane;
@@ -1667,8 +1495,8 @@ __device__ __forceinline__ int splat_step_split(const TrainSplatArgs &A, int bas
     float pnew[5];
     uint2 hull = make_uint2(0u, 0u);
     // GSVC_TRAIN_DETERMINISTIC: the splat's (splat, tile) partials in bbox
-    // order plus the record's atomics, each half summing its own components in
-    // splat_step's order (the same bits per component)
+    // row-major order, then the record's atomics (the overflow: zero unless
+    // det_cap was too small), each half summing its own components
     long long db = 0, de = 0;
     if (A.det_off && have) {
         db = A.det_off[i];
@@ -1694,56 +1522,37 @@ __device__ __forceinline__ int splat_step_split(const TrainSplatArgs &A, int bas
         }
         const float f0 = A.feat[3 * ic], f1 = A.feat[3 * ic + 1], f2 = A.feat[3 * ic + 2];
         const float wv = A.rgbw ? A.rgbw[ic] : 1.0f;
-        float m[4], v[4], df[4], npg[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) m[e] = v[e] = df[e] = npg[e] = 0.0f;
+        AdanRows<3> sf;
+        AdanRows<1> sw;
         if (upd) {
-            ld_row<3>(A.state[2][0], ic, m);
-            ld_row<3>(A.state[2][1], ic, v);
-            ld_row<3>(A.state[2][2], ic, df);
-            ld_row<3>(A.state[2][3], ic, npg);
-            if (A.rgbw_train) {
-                ld_row<1>(A.state[3][0], ic, m + 3);
-                ld_row<1>(A.state[3][1], ic, v + 3);
-                ld_row<1>(A.state[3][2], ic, df + 3);
-                ld_row<1>(A.state[3][3], ic, npg + 3);
-            }
+            adan_rows_load(sf, A.state[2], ic);
+            if (A.rgbw_train) adan_rows_load(sw, A.state[3], ic);
         }
-        const float df0 = g1.y * wv, df1 = g1.z * wv, df2 = g1.w * wv;
-        const float dw = (g1.y * f0 + g1.z * f1) + g1.w * f2;
+        if constexpr (kStamp) splat_stamp(st, 1);
+        // activation VJP (GaussianSplats_Represent.py:57-70): * rgb_W
+        const float g[4] = {g1.y * wv, g1.z * wv, g1.w * wv, (g1.y * f0 + g1.z * f1) + g1.w * f2};
         float pc[4] = {f0, f1, f2, wv};
         if (!upd) {
             if (have) {
                 float *o = A.grads_out + 9 * (size_t)i;
-                o[5] = df0;
-                o[6] = df1;
-                o[7] = df2;
-                o[8] = A.rgbw_train ? dw : 0.0f;
+                o[5] = g[0];
+                o[6] = g[1];
+                o[7] = g[2];
+                o[8] = A.rgbw_train ? g[3] : 0.0f;
             }
         } else {
-            const float g[4] = {df0, df1, df2, dw};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int q = e < 3 ? 2 : 3;
-                if (q == 3 && !A.rgbw_train) continue;
-                if (A.first[q]) npg[e] = -(g[e] * A.S.clip);
-                pc[e] = adan_update(A.S, pc[e], g[e], m[e], v[e], df[e], npg[e]);
-            }
+            adan_rows_step(A.S, A.first[2], sf, pc, g);
+            if (A.rgbw_train) adan_rows_step(A.S, A.first[3], sw, pc + 3, g + 3);
             if (have) {
                 st_row<3>(A.feat, i, pc);
-                st_row<3>(A.state[2][0], i, m);
-                st_row<3>(A.state[2][1], i, v);
-                st_row<3>(A.state[2][2], i, df);
-                st_row<3>(A.state[2][3], i, npg);
+                adan_rows_store(A.state[2], i, sf);
                 if (A.rgbw_train) {
                     st_row<1>(A.rgbw, i, pc + 3);
-                    st_row<1>(A.state[3][0], i, m + 3);
-                    st_row<1>(A.state[3][1], i, v + 3);
-                    st_row<1>(A.state[3][2], i, df + 3);
-                    st_row<1>(A.state[3][3], i, npg + 3);
+                    adan_rows_store(A.state[3], i, sw);
                 }
             }
         }
+        if constexpr (kStamp) splat_stamp(st, 2);
 #pragma unroll
         for (int e = 0; e < 4; ++e) s_cp[grp][e][lane] = pc[e];
     } else {
@@ -1766,21 +1575,15 @@ __device__ __forceinline__ int splat_step_split(const TrainSplatArgs &A, int bas
         const float c0 = A.chol[3 * ic], c1 = A.chol[3 * ic + 1], c2 = A.chol[3 * ic + 2];
         const float x0 = A.xyz[2 * ic], x1 = A.xyz[2 * ic + 1];
         hull = A.carry ? A.chull[ic] : make_uint2(0u, 0u);
-        float m[5], v[5], df[5], npg[5];
-#pragma unroll
-        for (int e = 0; e < 5; ++e) m[e] = v[e] = df[e] = npg[e] = 0.0f;
+        AdanRows<2> sx;
+        AdanRows<3> sc;
         if (upd) {
-            ld_row<2>(A.state[0][0], ic, m);
-            ld_row<2>(A.state[0][1], ic, v);
-            ld_row<2>(A.state[0][2], ic, df);
-            ld_row<2>(A.state[0][3], ic, npg);
-            ld_row<3>(A.state[1][0], ic, m + 2);
-            ld_row<3>(A.state[1][1], ic, v + 2);
-            ld_row<3>(A.state[1][2], ic, df + 2);
-            ld_row<3>(A.state[1][3], ic, npg + 2);
+            adan_rows_load(sx, A.state[0], ic);
+            adan_rows_load(sc, A.state[1], ic);
         }
-        // 2D projection VJP, backward2d.cu:8-51 (splat_step's sequence)
-        float vl0 = 0.f, vl1 = 0.f, vl2 = 0.f, vmx = 0.f, vmy = 0.f;
+        if constexpr (kStamp) splat_stamp(st, 1);
+        // 2D projection VJP (project2d.h), g = {d_xyz 2, d_cholesky 3}
+        float g[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, vmx = 0.f, vmy = 0.f;
         float l11 = c0, l21 = c1, l22 = c2;
         if (A.chol_bound) {
             l11 = l11 + A.chol_bound[0];
@@ -1788,26 +1591,18 @@ __device__ __forceinline__ int splat_step_split(const TrainSplatArgs &A, int bas
             l22 = l22 + A.chol_bound[2];
         }
         if (rad > 0) {
-            const float X00 = r2.z, X01 = r0.w, X10 = X01, X11 = r2.w;
-            const float G00 = g0.z, G01 = g0.w, G10 = G01, G11 = g1x;
-            const float N00 = -X00, N01 = -X01, N10 = -X10, N11 = -X11;
-            const float P00 = N00 * G00 + N10 * G01;
-            const float P01 = N01 * G00 + N11 * G01;
-            const float P10 = N00 * G10 + N10 * G11;
-            const float P11 = N01 * G10 + N11 * G11;
-            const float V00 = P00 * X00 + P10 * X01;
-            const float V01 = P01 * X00 + P11 * X01;
-            const float V10 = P00 * X10 + P10 * X11;
-            const float V11 = P01 * X10 + P11 * X11;
-            const float g11 = V00, g12 = V10 + V01, g22 = V11;
-            vl0 = 2.0f * l11 * g11 + 2.0f * g12 * l21;
-            vl1 = 2.0f * l11 * g12 + 2.0f * l21 * g22;
-            vl2 = 2.0f * l22 * g22;
+            float v_cov2d[3], v_L[3];
+            project2d_vjp(r2.z, r0.w, r2.w, g0.z, g0.w, g1x, l11, l21, l22, v_cov2d, v_L);
+            g[2] = v_L[0];
+            g[3] = v_L[1];
+            g[4] = v_L[2];
             vmx = g0.x * A.hw;
             vmy = g0.y * A.hh;
         }
+        // activation VJP (GaussianSplats_Represent.py:57-70): tanh (+ bound: identity)
         const float t0 = tanhf(x0), t1 = tanhf(x1);
-        const float dx0 = vmx * (1.0f - t0 * t0), dx1 = vmy * (1.0f - t1 * t1);
+        g[0] = vmx * (1.0f - t0 * t0);
+        g[1] = vmy * (1.0f - t1 * t1);
         pnew[0] = x0;
         pnew[1] = x1;
         pnew[2] = c0;
@@ -1816,33 +1611,20 @@ __device__ __forceinline__ int splat_step_split(const TrainSplatArgs &A, int bas
         if (!upd) {
             if (have) {
                 float *o = A.grads_out + 9 * (size_t)i;
-                o[0] = dx0;
-                o[1] = dx1;
-                o[2] = vl0;
-                o[3] = vl1;
-                o[4] = vl2;
+#pragma unroll
+                for (int e = 0; e < 5; ++e) o[e] = g[e];
             }
         } else {
-            const float g[5] = {dx0, dx1, vl0, vl1, vl2};
-#pragma unroll
-            for (int e = 0; e < 5; ++e) {
-                const int q = e < 2 ? 0 : 1;
-                if (A.first[q]) npg[e] = -(g[e] * A.S.clip);
-                pnew[e] = adan_update(A.S, pnew[e], g[e], m[e], v[e], df[e], npg[e]);
-            }
+            adan_rows_step(A.S, A.first[0], sx, pnew, g);
+            adan_rows_step(A.S, A.first[1], sc, pnew + 2, g + 2);
             if (have) {
                 st_row<2>(A.xyz, i, pnew);
-                st_row<2>(A.state[0][0], i, m);
-                st_row<2>(A.state[0][1], i, v);
-                st_row<2>(A.state[0][2], i, df);
-                st_row<2>(A.state[0][3], i, npg);
+                adan_rows_store(A.state[0], i, sx);
                 st_row<3>(A.chol, i, pnew + 2);
-                st_row<3>(A.state[1][0], i, m + 2);
-                st_row<3>(A.state[1][1], i, v + 2);
-                st_row<3>(A.state[1][2], i, df + 2);
-                st_row<3>(A.state[1][3], i, npg + 2);
+                adan_rows_store(A.state[1], i, sc);
             }
         }
+        if constexpr (kStamp) splat_stamp(st, 2);
     }
     __syncthreads();
     if (have && upd && A.carry && !(w & 1)) {
@@ -1850,6 +1632,7 @@ __device__ __forceinline__ int splat_step_split(const TrainSplatArgs &A, int bas
                             s_cp[grp][1][lane], s_cp[grp][2][lane], s_cp[grp][3][lane]};
         hits = carry_splat(A, i, p, hull);
     }
+    if constexpr (kStamp) splat_stamp(st, 3);  // (a colour wave has no carry: the barrier)
     return hits;
 }
 
@@ -1868,13 +1651,7 @@ __global__ __launch_bounds__(256) void train_splat_kernel(TrainSplatArgs A) {
         if (kStamp) splat_stamp(st, 5);
         return;
     }
-    int hits;
-    if (!kStamp && A.split) {
-        hits = splat_step_split(A, (blockIdx.x - 1) * 128);
-    } else {
-        const int t = (blockIdx.x - 1) * blockDim.x + threadIdx.x;
-        hits = t < A.n ? splat_step<kStamp>(A, t, st) : 0;
-    }
+    const int hits = splat_step<kStamp>(A, (blockIdx.x - 1) * 128, st);
     if (A.carry) {
         // the next frame's M is read only as M >= 1 (the tile kernel's background
         // branch, rasterize_sum.py:121-127): one plain store of 1 per wave that
@@ -2197,21 +1974,18 @@ static int train_step_impl(int num_points, float *xyz, float *cholesky,
         P.m_next = f.m_clear;  // frame_index + 1's M slot (the tile kernel zeroed it)
     }
     P.loss_seq = loss_seq;
-    // one extra (first) workgroup sums the loss, beside the splat workgroups
-    // two waves per 64 splats (splat_step_split: the carry in the geometry
-    // wave) unless GSVC_KNOB_SPLAT_ONE_LANE = 1 (nine lanes per splat, one per
-    // parameter element, was measured, round 6: 18.6 vs 10.5 us,
-    // profiles/r06/splat_elem/)
-    P.split = knob(GSVC_KNOB_SPLAT_ONE_LANE) != 1 ? 1 : 0;
-    const int per_block = P.split ? 128 : 256;
-    const int blocks = (num_points > 0 ? ceil_div(num_points, per_block) : 0) + 1;
+    // one extra (first) workgroup sums the loss, beside the splat workgroups of
+    // 128 splats each: two waves per 64 splats, the carry in the geometry wave
+    // (nine lanes per splat, one per parameter element, was measured, round 6:
+    // 18.6 vs 10.5 us, profiles/r06/splat_elem/)
+    const int blocks = (num_points > 0 ? ceil_div(num_points, 128) : 0) + 1;
     hipEvent_t tev[2];
     const int tslot = timing_begin(s, tev, kTimingTrainSplat);
     bool launched = false;
     if constexpr (kDiag) {
-        if (knob(GSVC_KNOB_STAMP) == 4 && debug_ptr()) {  // diagnostic: per-wave stamps of the splat kernel
+        if (knob(GSVC_KNOB_STAMP) == 4 && debug_ptr()) {  // diagnostic: stamps of the 4 * blocks waves
             P.stamps = reinterpret_cast<long long *>(debug_ptr());
-            hipLaunchKernelGGL(train_splat_kernel<true>, dim3(ceil_div(num_points, 256) + 1), dim3(256), 0, s, P);
+            hipLaunchKernelGGL(train_splat_kernel<true>, dim3(blocks), dim3(256), 0, s, P);
             launched = true;
         }
     }

@@ -20,10 +20,15 @@ class Knob(IntEnum):
     BATCH_ID_SLABS = 25
     KEEP_ORDER = 27
     ALPHA_BWD_ABLATE = 30
-    SPLAT_ONE_LANE = 34
     SPARSE_ABLATE = 36
     GENERIC_RENDER = 38
     RENDER_STAMPS = 39
 
 
-RETIRED = (1, 2, 4, 6, 7, 9, 10, 11, 12, 16, 17, 18, 20, 21, 22, 23, 26, 28, 29, 31, 32, 33, 35, 37)
+# A retired knob's name still resolves to its number (a plain attribute, not a
+# member: ``for k in Knob`` is the live list), so a stale caller that names it
+# stops where every retired number does -- gsvc_debug_set's -1 -- and not on
+# an AttributeError while its module is imported.
+Knob.SPLAT_ONE_LANE = 34
+
+RETIRED = (1, 2, 4, 6, 7, 9, 10, 11, 12, 16, 17, 18, 20, 21, 22, 23, 26, 28, 29, 31, 32, 33, 34, 35, 37)

@@ -35,14 +35,13 @@ enum gsvc_knob {
     GSVC_KNOB_BATCH_ID_SLABS = 25,   /* 1: batched frames render over id slabs too; exact */
     GSVC_KNOB_KEEP_ORDER = 27,       /* 1: the ordered projection at any density (no plain projection of sparse frames); exact */
     GSVC_KNOB_ALPHA_BWD_ABLATE = 30, /* alpha backward: 1, 2 skip phases of the kernel; ablation */
-    GSVC_KNOB_SPLAT_ONE_LANE = 34,   /* 1: the splat kernel's one-lane-per-splat layout, not two waves per 64 splats; exact */
     GSVC_KNOB_SPARSE_ABLATE = 36,    /* sparse composite bits: 1 no blend, 2 no stores, 4 no record loads, 8 no ranking, 16 no loads at all; ablation */
     GSVC_KNOB_GENERIC_RENDER = 38,   /* 1: the single-frame render by the generic id-slab kernel, not the two-tile one; exact */
     GSVC_KNOB_RENDER_STAMPS = 39     /* 1: the id-slab composite stamps its phases into the gsvc_debug_set_ptr buffer; exact */
 };
 /* Retired, never reuse (their A/Bs are finished; DESIGN.md §1c names the
  * section that holds each verdict): 1, 2, 4, 6, 7, 9, 10, 11, 12, 16, 17, 18,
- * 20, 21, 22, 23, 26, 28, 29, 31, 32, 33, 35, 37. */
+ * 20, 21, 22, 23, 26, 28, 29, 31, 32, 33, 34, 35, 37. */
 
 /* Sets knob ``key`` (an enum gsvc_knob) and returns its previous value; -1
  * for any key that is not a live enumerator, retired numbers included. */

@@ -14,8 +14,6 @@ overflow 256 (the bbox rebuild), and splats leaving / entering the image.
 import pytest
 import torch
 
-from gsvc_amd.knobs import Knob
-
 pytestmark = pytest.mark.gpu
 
 
@@ -82,19 +80,6 @@ def test_carried_fast_motion_and_overflow(cuda, deterministic, every):
     a = _run(cuda, True, 128, 192, 6000, 40, lr=0.05, edit=pile, rebuild=1000)
     b = _run(cuda, False, 128, 192, 6000, 40, lr=0.05, edit=pile)
     _same(a, b)
-
-
-@pytest.mark.parametrize("pair", [(Knob.SPLAT_ONE_LANE, 1)])
-def test_splat_kernel_layouts_bitwise(cuda, deterministic, pair):
-    """The splat kernel's layouts (train.hip): one lane per splat (Knob.SPLAT_ONE_LANE = 1)
-    and the product's two waves with the carry in the geometry wave -- the same op
-    sequence per element, so bitwise the same trajectory, deterministic
-    partial sums included, through a bin rebuild."""
-    from conftest import knobs
-    ref = _run(cuda, True, 256, 256, 2000, 70)
-    with knobs(pair):
-        got = _run(cuda, True, 256, 256, 2000, 70)
-    _same(ref, got)
 
 
 def test_carried_bins_trained_density(cuda, deterministic):

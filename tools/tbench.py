@@ -42,7 +42,8 @@ def main():
     ap.add_argument("--proj-stamps", action="store_true",
                     help="also stamp the projection kernel's waves (start, projected, inserted, end)")
     ap.add_argument("--splat-stamps", action="store_true",
-                    help="also stamp the splat kernel's waves (start, operands, Adan, carry, M, end)")
+                    help="also stamp the splat kernel's waves, two per 64 splats: a geometry and a colour "
+                         "half (start, operands, Adan, carry -- a colour wave: the barrier --, M, end)")
     ap.add_argument("--rebuild-every", type=int, default=None,
                     help="steps between carried-bin rebuilds (gsvc_amd.train.CARRY_REBUILD_EVERY)")
     ap.add_argument("--order-every", type=int, default=None,
@@ -201,7 +202,9 @@ def main():
         import numpy as np
         from gsvc_amd import _lib as L
         lib = L.load()
-        st = torch.zeros(((a.splats + 255) // 256 * 4 + 8, 8), dtype=torch.int64, device=dev)
+        # the step's launch: a loss workgroup, then one 4-wave workgroup per 128 splats
+        n_now = int(model._xyz.shape[0])
+        st = torch.zeros((((n_now + 127) // 128 + 1) * 4, 8), dtype=torch.int64, device=dev)
         lib.gsvc_debug_set_ptr(ctypes.c_void_p(st.data_ptr()))
         lib.gsvc_debug_set(Knob.STAMP, 4)
         model.train_iter(gt, a.warmup + a.iters + 400)
