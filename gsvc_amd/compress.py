@@ -618,9 +618,12 @@ def unpack_frames(streams: Sequence[bytes], device, cholesky_bound=None, prev=No
     return xq, Lq, cq, Lpre, sizes, (int(hw[0]), int(hw[1]))
 
 
-def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: bool = False):
+def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: bool = False,
+                  output: str = "rgb", reference=None):
     """Frame streams (``encode_frame``, either version, in any mix) to images
-    [F, 3, H, W].
+    [F, 3, H, W], or with ``output="i420"`` to 8-bit planar I420 frames, uint8
+    [F, H*W*3/2] (``video.rgb_to_i420`` of those images; with ``reference``,
+    the source's I420 frames, the pair (frames, int64 [F, 3] squared error)).
 
     On a HIP device: one unpack launch for all frames, then
     ``render_frames_sum``.  A delta frame adds the DECODED parameters of the
@@ -628,6 +631,10 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
     (``return_state=True`` also returns (xq, Lpre, cq) of the last frame).
     CPU: the numpy decoder and the CPU operators, frame by frame."""
     device = torch.device(device)
+    if output not in ("rgb", "i420"):
+        raise ValueError(f"decode_frames: output is 'rgb' or 'i420', not {output!r}")
+    if reference is not None and output != "i420":
+        raise ValueError("decode_frames: reference frames are compared in I420 (output='i420')")
     if len(streams) == 0:
         raise ValueError("decode_frames: no frames")
     if device.type == "cuda":
@@ -654,6 +661,9 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
         imgs = torch.stack(imgs).contiguous()
         xq, _, cq, Lpre = frames[-1]
         state = tuple(torch.from_numpy(np.ascontiguousarray(t)) for t in (xq, Lpre, cq))
+    if output == "i420":
+        from .video import rgb_to_i420
+        imgs = rgb_to_i420(imgs, reference)
     return (imgs, state) if return_state else imgs
 
 

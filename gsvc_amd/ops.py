@@ -528,7 +528,8 @@ def adan_step(params, grads, exp_avgs, exp_avg_sqs, exp_avg_diffs, neg_pre_grads
               beta2, beta3, bias_correction1, bias_correction2, bias_correction3_sqrt, lr,
               weight_decay, eps, no_prox, clip_global_grad_norm):
     """One fused Adan update of every tensor (gsvc_adan_step); same keyword
-    arguments as _multi_tensor_adan.  Tensors must be contiguous fp32 CUDA."""
+    arguments as _multi_tensor_adan.  Tensors must be contiguous fp32, all
+    CUDA (the kernel) or all CPU (the same op sequence in torch ops)."""
     import ctypes
     lists = (params, grads, exp_avgs, exp_avg_sqs, exp_avg_diffs, neg_pre_grads)
     n = len(params)
@@ -536,6 +537,25 @@ def adan_step(params, grads, exp_avgs, exp_avg_sqs, exp_avg_diffs, neg_pre_grads
         return
     if any(len(x) != n for x in lists):
         raise RuntimeError("adan_step: tensor lists differ in length")
+    if all(t.device.type == "cpu" and t.dtype == torch.float32 for group in lists for t in group):
+        # CPU tensors: csrc/adan.h's op sequence in torch ops (the device dispatch
+        # of quantize._forward_torch; the codec's encoder on a host without a GPU)
+        step, step_diff = lr / bias_correction1, lr * beta2 / bias_correction2
+        for p, grad, m, v, df, npg in zip(*lists):
+            g = grad * float(clip_global_grad_norm)
+            d = npg + g
+            m.mul_(beta1).add_(g, alpha=1 - beta1)
+            df.mul_(beta2).add_(d, alpha=1 - beta2)
+            t = d * beta2 + g
+            v.mul_(beta3).add_(t * t, alpha=1 - beta3)
+            den = v.sqrt() / bias_correction3_sqrt + eps
+            if no_prox:
+                p.mul_(1 - lr * weight_decay)
+            p.add_(m / den, alpha=-step).add_(df / den, alpha=-step_diff)
+            if not no_prox:
+                p.div_(1 + lr * weight_decay)
+            npg.copy_(-g)
+        return
     for group in lists:
         for t in group:
             if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():

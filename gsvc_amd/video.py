@@ -58,16 +58,85 @@ from .shard import aggregate_video_metrics, forced_k_frames, gops, shard_gops
 
 def i420_to_rgb(yuv: torch.Tensor, height: int, width: int) -> torch.Tensor:
     """One I420 frame (uint8 device tensor) -> [1, 3, H, W] float RGB in [0, 1]
-    (cv2.cvtColor(COLOR_YUV2RGB_I420) + ToTensor) on the GPU."""
+    (cv2.cvtColor(COLOR_YUV2RGB_I420) + ToTensor) on the GPU.  A uint8 CPU
+    tensor takes the kernel's arithmetic in torch integer ops (the codec's
+    encoder on a host without a GPU)."""
     from . import _lib as L
-    if not yuv.is_cuda or yuv.dtype != torch.uint8:
-        raise RuntimeError("yuv must be a uint8 CUDA tensor")
+    if yuv.dtype != torch.uint8:
+        raise RuntimeError("yuv must be a uint8 tensor")
     if yuv.numel() != height * width * 3 // 2:
         raise ValueError("yuv must hold one I420 frame of H*W*3/2 bytes")
+    if not yuv.is_cuda:
+        h, w, n, cn = int(height), int(width), height * width, (height // 2) * (width // 2)
+        flat = yuv.reshape(-1).to(torch.int64)
+        y = (flat[:n].view(h, w) - 16).clamp_min(0) * 1220542 + (1 << 19)
+        u, v = ((flat[n + k * cn:n + (k + 1) * cn].view(h // 2, w // 2) - 128)
+                .repeat_interleave(2, 0).repeat_interleave(2, 1) for k in (0, 1))
+        rgb = torch.stack([y + 1673527 * v, y - 852492 * v - 409993 * u, y + 2116026 * u]) >> 20
+        return (rgb.clamp(0, 255).to(torch.float32) / 255.0)[None].contiguous()
     out = torch.empty((1, 3, height, width), dtype=torch.float32, device=yuv.device)
     L.call("gsvc_i420_to_rgb", L.ptr(yuv.contiguous()), int(height), int(width), L.ptr(out),
            L.stream(yuv.device))
     return out
+
+
+def _rgb_to_i420_torch(images: torch.Tensor, ref: Optional[torch.Tensor]):
+    """csrc/yuv_out.hip's arithmetic in torch integer ops (CPU tensors)."""
+    F_, _, H, W = images.shape
+    c = torch.where(images > 0, images, torch.zeros_like(images))  # NaN, -0 -> 0
+    c = torch.where(c < 1, c, torch.ones_like(c))
+    q = (c * 255.0 + 0.5).to(torch.int32)  # fp32: one rounding per op, then truncation
+    R, G, B = q[:, 0], q[:, 1], q[:, 2]
+    Y = (269484 * R + 528482 * G + 102760 * B + ((16 << 20) + (1 << 19))) >> 20
+    Rs, Gs, Bs = (t.view(F_, H // 2, 2, W // 2, 2).sum(dim=(2, 4), dtype=torch.int32) for t in (R, G, B))
+    U = (-155188 * Rs - 305135 * Gs + 460324 * Bs + ((128 << 22) + (1 << 21))) >> 22
+    V = (460324 * Rs - 385875 * Gs - 74448 * Bs + ((128 << 22) + (1 << 21))) >> 22
+    out = torch.cat([t.clamp(0, 255).to(torch.uint8).reshape(F_, -1) for t in (Y, U, V)], dim=1)
+    if ref is None:
+        return out
+    d = out.to(torch.int64) - ref.to(torch.int64)
+    d = d * d
+    n, cn = H * W, H * W // 4
+    sse = torch.stack([d[:, :n].sum(1), d[:, n:n + cn].sum(1), d[:, n + cn:].sum(1)], dim=1)
+    return out, sse
+
+
+def rgb_to_i420(images: torch.Tensor, ref: Optional[torch.Tensor] = None):
+    """Float RGB images [F, 3, H, W] (or [3, H, W]; any values) -> planar 8-bit
+    I420 frames, uint8 [F, H*W*3/2]: per frame Y, then U and V of half size
+    each way (``gsvc_rgb_to_i420``, csrc/yuv_out.hip: BT.601 limited range,
+    chroma from the 2x2 block's sum; the inverse of ``i420_to_rgb``).  With
+    ``ref`` (source I420 frames, uint8, the output's shape) also returns the
+    exact sums of squared byte differences, int64 [F, 3] (Y, U, V).  CUDA
+    tensors take the kernel, CPU tensors the same arithmetic in torch integer
+    ops; the bytes are the same."""
+    if images.dim() == 3:
+        images = images[None]
+    if images.dim() != 4 or images.shape[1] != 3 or not images.is_floating_point():
+        raise ValueError("images must be a float tensor [F, 3, H, W] or [3, H, W]")
+    F_, _, H, W = (int(s) for s in images.shape)
+    if F_ <= 0 or H <= 0 or W <= 0 or H % 2 or W % 2:
+        raise ValueError("rgb_to_i420: at least one frame; height and width positive and even")
+    size = H * W * 3 // 2
+    if ref is not None:
+        if ref.dtype != torch.uint8 or ref.numel() != F_ * size or ref.device != images.device:
+            raise ValueError(f"ref must hold {F_} I420 frames of {size} bytes (uint8) on the images' device")
+        ref = ref.reshape(F_, size)
+    if not images.is_cuda:
+        return _rgb_to_i420_torch(images.detach().float(), ref)
+    from . import _lib as L
+    src = images.detach()
+    if src.dtype is not torch.float32 or not src.is_contiguous():
+        src = src.float().contiguous()
+    out = torch.empty((F_, size), dtype=torch.uint8, device=src.device)
+    sse = None
+    if ref is not None:
+        if not ref.is_contiguous():
+            ref = ref.contiguous()
+        sse = torch.empty((F_, 3), dtype=torch.int64, device=src.device)
+    L.call("gsvc_rgb_to_i420", F_, L.ptr(src), H, W, L.ptr(out), L.ptr(ref), L.ptr(sse),
+           L.stream(src.device))
+    return out if ref is None else (out, sse)
 
 
 def load_yuv_frames(path: str, width: int, height: int, device, frames: Optional[Sequence[int]] = None):

@@ -55,7 +55,8 @@ enum gsvc_status {
  * library (gsvc_amd_diag.h); GSVC_ERR_CAPTURE added.
  * ABI version 3: gsvc_encode_stream_bytes / gsvc_encode_stream added.
  * ABI version 4: gsvc_quant_train_workspace_bytes / gsvc_quant_train_step /
- * gsvc_quant_adan_step added. */
+ * gsvc_quant_adan_step added.  gsvc_rgb_to_i420 joined version 4 later: an
+ * added entry, nothing existing changed. */
 #define GSVC_ABI_VERSION 4
 
 /* Library identity and error reporting. */
@@ -639,6 +640,22 @@ int gsvc_rasterize_backward(
  * U and V (H/2)*(W/2) each, device memory) to out [3,H,W] float RGB / 255 with
  * OpenCV's COLOR_YUV2RGB_I420 fixed-point BT.601 arithmetic.  H, W even. */
 int gsvc_i420_to_rgb(const unsigned char *yuv, int height, int width, float *out, void *stream);
+
+/* Video output (not in the reference, which writes no YUV): the inverse of the
+ * above for a batch.  rgb [frames][3][H][W] fp32 (any values), out frames *
+ * (H*W*3/2) bytes: per frame Y (H*W), U, V ((H/2)*(W/2) each).  Per channel
+ * q = (int)(min(max(x, 0), 1) * 255 + 0.5) (NaN -> 0); Y = (269484 R + 528482 G
+ * + 102760 B + (16 << 20) + (1 << 19)) >> 20; with Rs, Gs, Bs the sums of q over
+ * a 2x2 block, U = (-155188 Rs - 305135 Gs + 460324 Bs + (128 << 22) + (1 << 21))
+ * >> 22 and V = (460324 Rs - 385875 Gs - 74448 Bs + ...) >> 22 (BT.601 limited
+ * range; int32; saturated to [0, 255]).
+ * ref: NULL, or source I420 frames in out's layout; then sse[frames][3] (Y, U, V)
+ * receives the exact integer sums of squared byte differences (the entry zeroes
+ * sse on the stream first).  H, W even, > 0.  Any alignment: W % 8 == 0 with rgb
+ * 16-byte and out / ref 8-byte aligned takes the vector kernel, everything else
+ * the bytewise one; both write the same bytes. */
+int gsvc_rgb_to_i420(int frames, const float *rgb, int height, int width, unsigned char *out,
+                     const unsigned char *ref, unsigned long long *sse, void *stream);
 
 /* ---- SSIM / MS-SSIM (the loss_fn SSIM variants, utils.py:29-40, and the
  * per-frame MS-SSIM metric, train_video_Represent.py:145), restating
