@@ -143,6 +143,17 @@ __device__ __forceinline__ long long tstamp() {
     return t;
 }
 
+// Diagnostic only (the band kernel's stamp slot 7): where the wave runs, as
+// XCC_ID << 32 | HW_ID (gfx9 layout: wave 3:0, SIMD 5:4, pipe 7:6, CU 11:8,
+// SH 12, SE 15:13), so the stamps give the resident workgroups per CU over
+// time and each tile's wave slot (tools/tile_resident.py, profiles/tile_resident/).
+__device__ __forceinline__ long long hw_where() {
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    return (long long)(((unsigned long long)(xcc & 15u) << 32) | hw);
+}
+
 // 8 workgroups per CU: <= 64 VGPRs (launch bound: 8 waves per SIMD) and
 // <= 20 KB of LDS (16-bit rectangles and item offsets).
 template <bool kStamp>
@@ -909,7 +920,11 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     }
     __syncthreads();
     if (carry && (!dense || brute)) n = S.nsel;
-    __builtin_amdgcn_s_setprio(0);
+    // The forward runs at priority 1, above other waves' loss and backward
+    // (0): at equal priority the arbiter serves the oldest wave, the young wave
+    // slots' forwards starve, and the kernel ends on their successors -- a long
+    // drain (profiles/tile_resident/).
+    __builtin_amdgcn_s_setprio(1);
     if (kStamp && tid == 0) st[1] = tstamp();
 
     // 2. forward: this wave's band against the entries that can reach it
@@ -1067,6 +1082,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     if (dense)
         for (int j = tid; j < n; j += kBThreads) kpark[j] = s_key[j];
     if (kStamp && tid == 0) st[2] = tstamp();
+    __builtin_amdgcn_s_setprio(0);  // (the forward's priority ends here)
 
     // 3. clamp, loss gradient (mse_loss backward: norm * (a - b); l1: norm * sgn),
     // clamp backward (passes where 0 <= out <= 1), error sums; v_out planes
@@ -1365,6 +1381,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         st[4] = tstamp();
         st[5] = tstamp();
         st[6] = n_all;  // the tile's entry count, for per-density breakdowns
+        st[7] = hw_where();
     }
 }
 
