@@ -60,7 +60,9 @@ struct TrainTileArgs {
     // kept because the band kernel's code follows it: without these words the
     // deterministic carry instance spills 18 SGPRs instead of 8 (kernel resource
     // remarks; moving the live fields instead changed all four instances).
-    int unused0[2];
+    int tgt16;        // band kernel: the targets as whole-tile 16-byte loads (img_w % 4 == 0 and
+                      // gt 16-byte aligned: train_step_impl), else the 4-byte pair loads
+    int unused0[1];
     int grouped;      // band kernel forward: lane-group entry lists (GSVC_KNOB_TILE_NO_GROUPS = 1: off)
     int diag;         // GSVC_KNOB_TILE_ABLATE (timing experiments only; wrong results):
                       // bits 2 no backward, 4 no forward
@@ -463,6 +465,8 @@ __global__ __launch_bounds__(256, 8) void train_tile_kernel(TrainTileArgs A) {
 // not formed.
 constexpr int kBSpec = 32;    // slab slots loaded with the count (64: slower, measured)
 constexpr int kBChunk = 64;   // entries staged at a time
+constexpr int kBIds = kBChunk;  // carried bins: candidate ids loaded with the count -- all a sparse
+                                // tile can have (4 bytes each, not kBSpec's 48-byte records)
 // rows wider than this split into two work items.  16 = never:
 // measured 51.6 vs 54.0 us (10) at trained density, 31.8 vs 32.1 at init --
 // fewer rounds of segmented sums beat the longer pixel loops once items are
@@ -701,6 +705,8 @@ struct BandLds {
 };
 // the order phase reads part row 0 as int4s (ids at [0, 64), candidates at [64, 128))
 static_assert(offsetof(BandLds, part) % 16 == 0, "BandLds.part must be 16-byte aligned");
+// the whole-tile targets: three 1 KiB pieces of 16 bytes a lane at the planes' start
+static_assert(offsetof(BandLds, v) % 16 == 0 && 3 * kTilePix <= 3 * kTile * kVRow, "BandLds.v holds the targets");
 
 // kDet: GSVC_TRAIN_DETERMINISTIC's slot stores in place of the atomics (its
 // own instantiation: the slot arithmetic in the flush would cost the atomic
@@ -737,9 +743,9 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     // one round trip for everything the tile starts from, with no wait in
     // between (a branch around a load makes the compiler wait for it at the
     // join): the frame's M and this tile's count (scalar), the first kBSpec
-    // slab records (lanes past kBSpec re-read slot 0: the same lines), the
-    // pair's targets (lanes outside the image read pixel 0; only the loss
-    // reads them, masked)
+    // slab records (lanes past kBSpec re-read slot 0: the same lines) or, with
+    // carried bins, wave 0's kBIds candidate ids (ids past the count are loaded
+    // and never used), the targets (below)
     constexpr bool carry = kCarry;
     const int m_frame = *A.m_dev;
     const unsigned cnt_raw = A.counts[tile];
@@ -748,22 +754,43 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     int cid = 0;  // carried bins: the lane's candidate id
     int *tcids = carry ? A.cids + (size_t)tile * kTrainCarryCap : nullptr;
     if (carry) {
-        cid = tcids[tid < kBSpec ? tid : 0];
+        cid = tcids[tid < kBIds ? tid : 0];  // (a tile's list holds kTrainCarryCap: in bounds)
     } else {
         const float4 *h0 = slab_rec(A.slab, A.ntiles, tile, tid < kBSpec ? tid : 0);
         r0 = h0[0];
         r1 = h0[1];
         r2 = h0[2];
     }
-    // the pair's targets go straight into LDS (global_load_lds: no VGPRs held
-    // over the order and forward phases -- held in registers they spilled, and
-    // the spill's vmcnt(0) cost the carried-bins kernel a round trip), into the
-    // v_out planes' space, [wave][c][q][lane], which the loss phase overwrites
-    // only after every wave has read its targets back
+    // the targets go straight into LDS (global_load_lds: no VGPRs held over
+    // the order and forward phases -- held in registers they spilled, and the
+    // spill's vmcnt(0) cost the carried-bins kernel a round trip), into the
+    // v_out planes' space, which the loss phase overwrites only after every
+    // wave has read its targets back.
+    // A.tgt16 (rows of whole, aligned 16-byte groups): three 16-byte loads a
+    // tile, one per channel, all from wave 1 -- lane L the pixels
+    // 4 (L & 3) .. + 3 of tile row L >> 2, 16 whole 64-byte lines an
+    // instruction, as [c][16 rows][16 px].  Wave 0, whose round trips are the
+    // order phase, has no target load in its queue; wave 1 waits for them
+    // before the barrier that ends the order.  Rows and groups outside the
+    // image load the last row / group inside it (img_w % 4 == 0: no group
+    // straddles the edge; nothing past a plane's end).
+    // Otherwise: each wave its pixel pairs, 4 bytes a lane, as [wave][c][q][lane]
+    // (lanes outside the image read pixel 0).  Only the loss reads either, masked.
     float *sgt = &S.v[0][0] + w * (6 * 64);
-    {
-        typedef __attribute__((address_space(1))) void gvoid;
-        typedef __attribute__((address_space(3))) void lvoid;
+    typedef __attribute__((address_space(1))) void gvoid;
+    typedef __attribute__((address_space(3))) void lvoid;
+    const bool tgt16 = A.tgt16 != 0;
+    auto load_tile_targets = [&]() {
+        const int gi = min(ty * kTile + (lane >> 2), A.img_h - 1);
+        const int gj = min(tx * kTile + ((lane & 3) << 2), A.img_w - 4);
+        const float *g = A.gt + (size_t)gi * (size_t)A.img_w + (size_t)gj;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            __builtin_amdgcn_global_load_lds((gvoid *)(g + c * hw), (lvoid *)(&S.v[0][0] + c * kTilePix), 16, 0, 0);
+    };
+    if (tgt16) {
+        if (w == 1) load_tile_targets();
+    } else {
         const size_t b0 = nin > 0 ? pix0 : 0, b1 = nin > 1 ? pix0 + 1 : b0;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -795,7 +822,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         // <= 64 candidates: wave 0 gathers their records and boxes by id, keeps
         // the tile's entries and ranks them by id (the others rank last)
         if (w == 0) {
-            if (lane >= kBSpec && lane < n) cid = tcids[lane];
+            // (every lane's id came with the count: no second, dependent trip for lanes 32-63)
             bool mem = false;
             if (lane < n) {
                 const uint2 b = A.cbox[cid];
@@ -918,6 +945,9 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             wave_sorted_tile_ids(ids, n, s_key, reinterpret_cast<unsigned *>(&S.part[4][0]));
         }
     }
+    // wave 1's whole-tile targets have landed before it arrives: past the
+    // barrier either wave may read them
+    if (tgt16 && w == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (carry && (!dense || brute)) n = S.nsel;
     // The forward runs at priority 1, above other waves' loss and backward
@@ -1089,11 +1119,22 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     {
         const float o[3][2] = {{ar.x, ar.y}, {ag.x, ag.y}, {ab.x, ab.y}};
         float gt[3][2];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the targets' global_load_lds
+        if (tgt16) {
+            // (landed before the order's barrier) the pair as one 8-byte read per channel
+            const float *sp = &S.v[0][0] + prow * kTile + pcol;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            gt[c][0] = sgt[(2 * c) * 64 + lane];
-            gt[c][1] = sgt[(2 * c + 1) * 64 + lane];
+            for (int c = 0; c < 3; ++c) {
+                const float2 t = *reinterpret_cast<const float2 *>(sp + c * kTilePix);
+                gt[c][0] = t.x;
+                gt[c][1] = t.y;
+            }
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the targets' global_load_lds
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                gt[c][0] = sgt[(2 * c) * 64 + lane];
+                gt[c][1] = sgt[(2 * c + 1) * 64 + lane];
+            }
         }
         float se = 0.f, ae = 0.f;
         float v[3][2];
@@ -1886,7 +1927,9 @@ static int train_step_impl(int num_points, float *xyz, float *cholesky,
     T.rec = w.f.rec;
     T.bg = background;
     T.gt = gt;
-    T.grad = reinterpret_cast<float *>(w.grad);
+    // whole-tile target loads: every row a whole number of 16-byte groups, each aligned
+    T.tgt16 = img_width % 4 == 0 && reinterpret_cast<uintptr_t>(gt) % 16 == 0;
+    T.grad =reinterpret_cast<float *>(w.grad);
     T.err = w.err;
     T.out = render_out;
     T.diag = knob(GSVC_KNOB_TILE_ABLATE);

@@ -102,6 +102,16 @@ def analyze(raw, name="stamps"):
         tot_t.append(t)
         tot_r.append(cur)
     tot_t, tot_r = np.array(tot_t), np.array(tot_r)
+    # the order phase (st[1] - st[0]) of every tile, and of each CU's first
+    # generation -- its first `peak` workgroups by start -- by wave 0's slot
+    order = (raw[:, 1] - raw[:, 0]) * 0.01
+    gen1 = np.zeros(len(raw), dtype=bool)
+    for c, pk in zip(cus, peak):
+        idx = np.nonzero(cu == c)[0]
+        gen1[idx[np.argsort(s[idx], kind="stable")[:pk]]] = True
+    slot = hw & 15
+    order_gen1_by_slot = {int(k): [round(float(np.percentile(order[gen1 & (slot == k)], p)), 2)
+                                   for p in (10, 50, 90)] for k in np.unique(slot[gen1])}
     full = np.nonzero(tot_r >= 0.95 * tot_r.max())[0]
     cap = float(np.sum(peak)) * end
     # the drain starts when the chip last falls below 95 % of its peak
@@ -116,7 +126,9 @@ def analyze(raw, name="stamps"):
         slot_refill_wait_us=q(refill) if refill else None,
         drain_us=round(end - float(tot_t[fall]), 2),
         slot_fill=round(1.0 - lost_total / cap, 4),
-        entries=q(raw[:, 6]))
+        entries=q(raw[:, 6]),
+        order_us=q(order), order_gen1_us=q(order[gen1]),
+        order_gen1_us_p10_p50_p90_by_wave_slot=order_gen1_by_slot)
 
 
 def main():
