@@ -42,6 +42,13 @@ struct SegIds {
     __device__ __forceinline__ int cap() const { return recs ? (ovf ? kCarryCap : kTilePix) : cap_ids; }
 };
 
+// The set bits of a wave mask (a ballot) below this lane: v_mbcnt_lo / _hi on
+// the mask's SGPRs, 2 VALU (popcll(m & ((1 << lane) - 1)) is 2 ands and 2 bit
+// counts on a per-lane 64-bit mask).
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
 __device__ __forceinline__ int rank_below(int v, int n) {
     // number of lanes k < n whose value is below v (ties impossible: ids unique)
     int rank = 0;

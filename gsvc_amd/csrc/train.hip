@@ -691,6 +691,19 @@ __device__ int wg_sorted_members(const int *cand, int n, const uint2 *cbox, unsi
     return min(written, kTilePix);
 }
 
+// What every entry of a staged chunk has in common, decided once by the wave
+// that stages it (each lane: its entry's facts, true without one): bit 0 every
+// colour is finite (the select-free blends), bit 1 every geometry is bounded
+// (geo_cut_ok; with bit 0: the sigma-threshold cut, forward and backward).  Both
+// waves read the word in the forward and in the backward; before, each of them
+// re-read the entries and took the ballots again in either phase.
+__device__ __forceinline__ int chunk_facts(bool fin, bool geo_ok) {
+    return (__ballot(!fin) == 0ull ? 1 : 0) | (__ballot(!geo_ok) == 0ull ? 2 : 0);
+}
+__device__ __forceinline__ bool colour_finite(float r, float g, float b) {
+    return __builtin_isfinite(r) && __builtin_isfinite(g) && __builtin_isfinite(b);
+}
+
 struct BandLds {
     float v[3][kTile * kVRow];     // v_out planes, rows padded to kVRow words
     float4 geo[kBChunk + 1];       // staged entries (rank order): x, y, a/2, b
@@ -702,6 +715,7 @@ struct BandLds {
     signed char perm[kBThreads];   // backward: per wave, the chunk's entries by item length
     int misc[4];   // the waves' error sums
     int nsel;      // carried bins: the tile's entries among its candidates
+    int cflag;     // the staged chunk's facts (chunk_facts), by the wave that staged it
 };
 // the order phase reads part row 0 as int4s (ids at [0, 64), candidates at [64, 128))
 static_assert(offsetof(BandLds, part) % 16 == 0, "BandLds.part must be 16-byte aligned");
@@ -836,7 +850,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             const bool sorted = A.csorted && (int)__builtin_amdgcn_readfirstlane(srt_raw) == n;
             if (sorted) {
                 // candidates in id order: a member's rank is the members below it
-                rank = __popcll(__ballot(mem) & ((1ull << lane) - 1ull));
+                rank = lanes_below(__ballot(mem));
             } else if (kDiag && (A.diag & 128)) {
                 rank = rank_below(id, n);
             } else {
@@ -868,14 +882,21 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                     if (lane == 0) A.csorted[tile] = (unsigned)n;
                 }
             }
+            bool efin = true, egeo = true;
             if (mem) {
                 S.geo[rank] = r0;
                 S.col[rank] = make_float4(r1.x, r1.z, r1.w, r2.x);
                 S.gid[rank] = id;
                 S.ro[rank] = ellipse_rect(r0.x, r0.y, 2.0f * r0.z, r0.w, 2.0f * r1.x, 1.0f, tx0, ty0);
+                efin = colour_finite(r1.z, r1.w, r2.x);
+                egeo = geo_cut_ok(r0, r1.x);
             }
             const int nm = __popcll(__ballot(mem));  // (the whole wave's ballot)
-            if (lane == 0) S.nsel = nm;
+            const int cf = chunk_facts(efin, egeo);
+            if (lane == 0) {
+                S.nsel = nm;
+                S.cflag = cf;
+            }
         }
     } else if (!dense) {
         if (tid >= kBSpec && tid < n) {
@@ -884,13 +905,20 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             r1 = h[1];
             r2 = h[2];
         }
-        if (w == 0 && lane < n) {
-            const int id = __float_as_int(r2.y);
-            const int rank = rank_below(id, n);
-            S.geo[rank] = r0;
-            S.col[rank] = make_float4(r1.x, r1.z, r1.w, r2.x);
-            S.gid[rank] = id;
-            S.ro[rank] = ellipse_rect(r0.x, r0.y, 2.0f * r0.z, r0.w, 2.0f * r1.x, 1.0f, tx0, ty0);
+        if (w == 0) {
+            bool efin = true, egeo = true;
+            if (lane < n) {
+                const int id = __float_as_int(r2.y);
+                const int rank = rank_below(id, n);
+                S.geo[rank] = r0;
+                S.col[rank] = make_float4(r1.x, r1.z, r1.w, r2.x);
+                S.gid[rank] = id;
+                S.ro[rank] = ellipse_rect(r0.x, r0.y, 2.0f * r0.z, r0.w, 2.0f * r1.x, 1.0f, tx0, ty0);
+                efin = colour_finite(r1.z, r1.w, r2.x);
+                egeo = geo_cut_ok(r0, r1.x);
+            }
+            const int cf = chunk_facts(efin, egeo);
+            if (lane == 0) S.cflag = cf;
         }
     } else if (brute) {
         unsigned *bm = reinterpret_cast<unsigned *>(&S.part[4][0]);
@@ -970,7 +998,9 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     const int y_lo = 8 * w, y_hi = 8 * w + 7;
     // dense: stage chunk [c0, c0 + cnt) of the order from the splats' records
     // (rec holds the slab's records by splat id)
+    // (cnt <= kBChunk = one wave's lanes: wave 0 stages, and decides the chunk's facts)
     auto stage_chunk = [&](const int *keys, int cnt) {
+        bool efin = true, egeo = true;
         if (tid < cnt) {
             const int key = keys[tid];
             const float4 *rr = A.rec + 3 * (size_t)key;
@@ -979,6 +1009,12 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             S.col[tid] = make_float4(b.x, b.z, b.w, c.x);
             S.gid[tid] = __float_as_int(c.y);
             S.ro[tid] = ellipse_rect(a.x, a.y, 2.0f * a.z, a.w, 2.0f * b.x, 1.0f, tx0, ty0);
+            efin = colour_finite(b.z, b.w, c.x);
+            egeo = geo_cut_ok(a, b.x);
+        }
+        if (w == 0) {
+            const int cf = chunk_facts(efin, egeo);
+            if (lane == 0) S.cflag = cf;
         }
     };
     // the forward's lane-group lists (A.grouped): [64 iterations][8 groups] entry
@@ -1000,7 +1036,6 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             // The pairs skipped contribute nothing (the band culling's own
             // argument), so every pixel sees the same sequence of blends.
             unsigned gm = 0u;
-            bool fin = false, cutok = false;
             if (lane < cnt) {
                 const unsigned rc = S.ro[lane];
                 if (rc != kNoRect) {
@@ -1011,29 +1046,27 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                     const unsigned cb = ((2u << cx1) - 1u) & ~((1u << cx0) - 1u);
                     gm = ((rb & 1u) ? cb : 0u) | ((rb & 2u) ? cb << 4 : 0u);
                 }
-                const float4 C = S.col[lane];
-                fin = __builtin_isfinite(C.y) && __builtin_isfinite(C.z) && __builtin_isfinite(C.w);
-                cutok = fin && geo_cut_ok(S.geo[lane], C.x);
             }
+            // the chunk's facts (chunk_facts, staged with it; an entry outside this
+            // band counts too: the slower blends give the same bits)
+            const int cf = __builtin_amdgcn_readfirstlane(S.cflag);
             if (kDiag && (A.diag & 4)) gm = 0u;  // diagnostic: no forward blending (wrong results)
             // row `lane` of the lists: the sentinel, then the entries
             *reinterpret_cast<unsigned long long *>(wlist + 8 * lane) = 0x4040404040404040ull;
             __builtin_amdgcn_wave_barrier();
-            const unsigned long long below = (1ull << lane) - 1ull;
+            // (the list lengths as ints: max(int, unsigned) is HIP's double overload,
+            // five f64 instructions a group in the parent's ISA)
             int maxlen = 0;
 #pragma unroll
             for (int g = 0; g < 8; ++g) {
                 const bool in = (gm >> g) & 1u;
                 const unsigned long long mg = __ballot(in);
-                if (in) wlist[8 * __popcll(mg & below) + g] = (unsigned char)lane;
-                maxlen = max(maxlen, __popcll(mg));
+                if (in) wlist[8 * lanes_below(mg) + g] = (unsigned char)lane;
+                maxlen = max(maxlen, (int)__popcll(mg));
             }
-            const unsigned long long any = __ballot(gm != 0u);
-            const unsigned long long fm = __ballot(fin);
-            const unsigned long long cm = __ballot(cutok);
             __builtin_amdgcn_wave_barrier();
             const unsigned char *ml = wlist + grp;
-            if ((any & ~cm) == 0) {
+            if ((cf & 3) == 3) {
                 // finite colours and geometry (the rule): the threshold cut
                 for (int it = 0; it < maxlen; ++it) {
                     const int k = ml[8 * it];
@@ -1044,7 +1077,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                     const float bdy = G.w * dy;
                     blend2_cut(G.x, G.z, bdy, cq, C.y, C.z, C.w, px, ar, ag, ab);
                 }
-            } else if ((any & ~fm) == 0) {
+            } else if (cf & 1) {
                 for (int it = 0; it < maxlen; ++it) {
                     const int k = ml[8 * it];
                     const float4 G = S.geo[k];
@@ -1137,7 +1170,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             }
         }
         float se = 0.f, ae = 0.f;
-        float v[3][2];
+        float v[3][2], d[3][2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const bool inside = q < nin;
@@ -1145,17 +1178,31 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float x = clamp_unit(o[c][q]);
-                const float d = x - gt[c][q];
-                pse = fmaf(d, d, pse);
-                pae += fabsf(d);
-                const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
-                const float gv = A.loss_l1 ? A.norm * sg : A.norm * d;
-                v[c][q] = (inside && o[c][q] >= 0.0f && o[c][q] <= 1.0f) ? gv : 0.0f;
+                d[c][q] = x - gt[c][q];
+                pse = fmaf(d[c][q], d[c][q], pse);
+                pae += fabsf(d[c][q]);
             }
             if (inside) {
                 se += pse;
                 ae += pae;
             }
+        }
+        // one branch on the loss kind (wave-uniform) around the six gradients: as a
+        // select per value the L2 step paid for the six signs as well
+        if (A.loss_l1) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float sg = d[c][q] > 0.0f ? 1.0f : (d[c][q] < 0.0f ? -1.0f : 0.0f);
+                    v[c][q] = (q < nin && o[c][q] >= 0.0f && o[c][q] <= 1.0f) ? A.norm * sg : 0.0f;
+                }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    v[c][q] = (q < nin && o[c][q] >= 0.0f && o[c][q] <= 1.0f) ? A.norm * d[c][q] : 0.0f;
         }
         if (A.out) {  // optional clamped render (tests)
 #pragma unroll
@@ -1224,7 +1271,6 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         // have similar lengths; each entry's sums are unchanged (its items
         // stay together, in row order)
         {
-            const unsigned long long below = (1ull << lane) - 1ull;
             int rank = 0, seen = 0;
             unsigned long long left = __ballot(true);
             if (kDiag && (A.diag & 64)) {  // A/B: entry order
@@ -1237,16 +1283,18 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             const int cls = ilen >= 9 ? 3 : (ilen >= 7 ? 2 : (ilen >= 5 ? 1 : 0));
             for (int L = 3; L >= 0 && left; --L) {
                 const unsigned long long m = __ballot(cls == L);
-                if (cls == L) rank = seen + __popcll(m & below);
-                seen += __popcll(m);
+                if (cls == L) rank = seen + lanes_below(m);
+                seen += (int)__popcll(m);
                 left &= ~m;
             }
             wperm[rank] = (signed char)lane;
         }
         __builtin_amdgcn_wave_barrier();
         // the chunk's geometry finite: the backward's alpha cut by threshold
-        const bool bcut =
-            __ballot(lane < gn && !geo_cut_ok(S.geo[lane], S.col[lane].x)) == 0ull;
+        // (and its colours: the threshold form multiplies a failing pixel's v_alpha
+        // by alpha = 0, which is NaN for a non-finite colour where the reference
+        // skips the pixel -- such a chunk keeps the test as written)
+        const bool bcut = (__builtin_amdgcn_readfirstlane(S.cflag) & 3) == 3;
         const int ent = wperm[lane];  // the entry in sorted slot `lane`
         const int sitems = __shfl(items, ent, 64);
         const int incl = wave_scan_dpp<false>(sitems, 0);
@@ -1306,6 +1354,11 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                 // offsets) with dx stepping by -1 (exact: ex - px is exact or,
                 // far off, rounds alike); a lane without pixel work: no trip
                 const float *vp = &S.v[0][0] + row * kVRow + cs;
+                // (diag 8 empties the range of every lane, the one at the planes' first
+                // word too, where vp - 1 lies below LDS address 0 and compares above
+                // vp: the walk would not end.  Without it a lane with no pixel work is
+                // past its entry's first row, or below the image.)
+                if (kDiag && (A.diag & 8)) vp = &S.v[0][0] + 1;
                 const float *const ve = rowok ? &S.v[0][0] + row * kVRow + ce : vp - 1;
                 float dx = ex - (tx0 + (float)cs);
                 // kCut: the chunk's geometry is finite, so the alpha cut is the

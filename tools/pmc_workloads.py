@@ -34,7 +34,25 @@ def main():
                     help="renders before the --iters summarised ones (bench.py times its renders "
                          "after warm-up; the first calls include the unordered projection and a "
                          "cold clock)")
+    ap.add_argument("--knob", action="append", default=[], metavar="NAME=VALUE",
+                    help="a diagnostic knob (gsvc_amd.knobs.Knob), e.g. TILE_ABLATE=8; needs "
+                         "GSVC_DIAG=1 (the diagnostic library).  train50k / oppath set it after "
+                         "the --settle iterations (an ablation's wrong gradients would train "
+                         "another frame), the other modes before the workload")
     a = ap.parse_args()
+
+    def set_knobs():
+        from gsvc_amd import _lib
+        from gsvc_amd.knobs import Knob
+        if a.knob and os.environ.get("GSVC_DIAG") != "1":
+            sys.exit("--knob needs GSVC_DIAG=1")
+        for kv in a.knob:
+            name, value = kv.split("=")
+            if _lib.load().gsvc_debug_set(int(Knob[name]), int(value)) < 0:
+                sys.exit(f"knob {name} refused")
+
+    if a.mode not in ("train50k", "oppath"):
+        set_knobs()
     from gsvc_amd.frame import make_frame_model, synthetic_gt
     dev = torch.device("cuda:0")
     H, W = 1080, 1920
@@ -75,6 +93,9 @@ def main():
         model = make_frame_model(H, W, 50000, dev, seed=1000)
         gt = synthetic_gt(H, W, 8, "cpu").to(dev)
         for it in range(1, a.settle + a.iters + 1):
+            if it == a.settle + 1:
+                torch.cuda.synchronize()
+                set_knobs()
             model.train_iter(gt, it)
         model.eval()
         if a.mode == "oppath":  # GSVC's own op sequence over the drop-in, on the trained frame
