@@ -66,6 +66,27 @@ __device__ __forceinline__ int wave_scan_dpp(int v, int id) {
     return v;
 }
 
+// The wave's sum as lane 0 gets it from the butterfly
+// ``for (off = 32; off; off >>= 1) v += __shfl_xor(v, off)``, bit for bit, with
+// no LDS traffic: xor 32 and 16 as v_permlane32_swap / v_permlane16_swap of the
+// value with itself (each lane then holds the two halves' / row pairs' values,
+// and a + b = b + a), xor 8 as row_ror:8, xor 4 as row_shl:4 (lane i reads
+// i + 4: the xor partner for the lanes with bit 2 clear), xor 2 and 1 as quad
+// permutes.  Only lane 0's result is the butterfly's (lanes with bit 2 set
+// differ after the row_shl step).  A shuffle step was a ds_bpermute and four
+// VALU of address arithmetic.
+__device__ __forceinline__ float wave_xor_sum_lane0(float v) {
+    auto fold = [&](auto pair) { v = __uint_as_float(pair[0]) + __uint_as_float(pair[1]); };
+    fold(__builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false));
+    fold(__builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false));
+    auto step = [&](int t) { v += __int_as_float(t); };
+    step(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, true));  // row_ror:8
+    step(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x104, 0xf, 0xf, true));  // row_shl:4
+    step(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, true));   // quad_perm:[2,3,0,1]
+    step(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, true));   // quad_perm:[1,0,3,2]
+    return v;
+}
+
 // One step of a segmented inclusive sum: lanes whose DPP source lane carries
 // the same key add its N sums (sources outside the row / masked rows: key -1,
 // and the lane is not written).  ``g += m * g[src]`` with m = 1 or 0 as ONE

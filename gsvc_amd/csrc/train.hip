@@ -1216,11 +1216,9 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             S.v[c][p] = v[c][0];
             S.v[c][p + 1] = v[c][1];
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            se += __shfl_xor(se, off, 64);
-            ae += __shfl_xor(ae, off, 64);
-        }
+        // (lane 0's sums in the xor butterfly's order 32 ... 1, as before, by DPP)
+        se = wave_xor_sum_lane0(se);
+        ae = wave_xor_sum_lane0(ae);
         if (lane == 0) {
             S.misc[2 * w] = __float_as_int(se);
             S.misc[2 * w + 1] = __float_as_int(ae);
@@ -1241,6 +1239,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     float *eacc = &S.part[0][0] + w * (8 * kBChunk);  // [8][kBChunk] entry sums per wave
     signed char *wown = S.own + w * 64;
     signed char *wperm = S.perm + w * 64;
+    const int rows_in = A.img_h - ty * kTile;  // the tile's rows inside the image (>= 1)
     for (int c0 = 0; c0 < n; c0 += kBChunk) {
         const int gn = min(kBChunk, n - c0);
         if (dense) {
@@ -1273,20 +1272,23 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         {
             int rank = 0, seen = 0;
             unsigned long long left = __ballot(true);
-            if (kDiag && (A.diag & 64)) {  // A/B: entry order
-                rank = lane;
-                left = 0ull;
-            }
-            // four length classes (9+, 7-8, 5-6, <= 4 and no items), entry
-            // order within a class: most of an exact sort's gain for a quarter
-            // of its VALU
-            const int cls = ilen >= 9 ? 3 : (ilen >= 7 ? 2 : (ilen >= 5 ? 1 : 0));
-            for (int L = 3; L >= 0 && left; --L) {
+            // four length classes (9+, 7-8, 5-6, <= 4), entry order within a
+            // class: most of an exact sort's gain for a quarter of its VALU.
+            // Entries without items in this band (and the lanes past the
+            // chunk) are a fifth class, ranked last -- what the four leave
+            // over, no compare of its own: the slots that carry items are a
+            // prefix of the sorted order, which the rounds' item -> slot
+            // count relies on.  The items' layout is what it was: those
+            // entries held none.
+            int cls = ilen >= 9 ? 4 : (ilen >= 7 ? 3 : (ilen >= 5 ? 2 : (items > 0 ? 1 : 0)));
+            if (kDiag && (A.diag & 64)) cls = items > 0 ? 1 : 0;  // A/B: entry order (no items: last)
+            for (int L = 4; L >= 1 && left; --L) {
                 const unsigned long long m = __ballot(cls == L);
                 if (cls == L) rank = seen + lanes_below(m);
                 seen += (int)__popcll(m);
                 left &= ~m;
             }
+            if (cls == 0) rank = seen + lanes_below(left);
             wperm[rank] = (signed char)lane;
         }
         __builtin_amdgcn_wave_barrier();
@@ -1297,6 +1299,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         const bool bcut = (__builtin_amdgcn_readfirstlane(S.cflag) & 3) == 3;
         const int ent = wperm[lane];  // the entry in sorted slot `lane`
         const int sitems = __shfl(items, ent, 64);
+        const int srect = __shfl((int)rc, ent, 64);  // ... and its rectangle (one trip per chunk, not per round)
         const int incl = wave_scan_dpp<false>(sitems, 0);
         const int off = incl - sitems;  // sorted slot `lane`'s first item
         const int total = __builtin_amdgcn_readlane(incl, 63);
@@ -1311,19 +1314,28 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         // v_mov_b32 of 337 VALU per round).  Same sums bit for bit.
         auto rounds = [&](auto kcut) {
             for (int base = 0; base < total; base += 64) {
-                // the entry of item base + lane: the last entry whose first item is <= it
+                // the sorted slot of item base + lane: the last slot whose first
+                // item is <= it.  The slots with items are the sorted order's
+                // prefix, first items ascending (the others, and the lanes past
+                // the chunk, start at `total`), so that is the slot that holds
+                // item `base` plus the runs that start in (base, base + lane]:
+                // the starts scattered through LDS, one ballot, and a lane count
+                // of the mask in SGPRs (before: a six-step DPP max-scan of the
+                // scattered slots)
                 wown[lane] = -1;
                 __builtin_amdgcn_wave_barrier();
                 if (sitems > 0 && off >= base && off < base + 64) wown[off - base] = (signed char)lane;
-                const int straddle = __popcll(__ballot(lane < gn && off <= base)) - 1;
+                const int straddle = __popcll(__ballot(off <= base)) - 1;
                 __builtin_amdgcn_wave_barrier();
-                int slot = max((int)wown[lane], straddle);
-                slot = wave_scan_dpp<true>(slot, -2147483647 - 1);  // sorted slot of item base + lane
+                const unsigned long long starts = __ballot(wown[lane] >= 0);
+                const int slot = straddle + lanes_below(starts >> 1);
                 const int item = base + lane;
-                // the entry, its first item and rectangle
-                const int own = __shfl(ent, slot, 64);
-                const int eoff = __shfl(off, slot, 64);
-                const unsigned ro = (unsigned)__shfl((int)rc, own, 64);
+                // the entry, its first item and rectangle: three reads of lane
+                // `slot` (in [0, 64): the permute's byte address as it stands),
+                // none waiting for another
+                const int own = __builtin_amdgcn_ds_bpermute(slot << 2, ent);
+                const int eoff = __builtin_amdgcn_ds_bpermute(slot << 2, off);
+                const unsigned ro = (unsigned)__builtin_amdgcn_ds_bpermute(slot << 2, srect);
                 const float4 G = S.geo[own], C = S.col[own];
                 const int j = item - eoff;  // item index within the entry
                 const int rx0 = (int)(ro & 15u), rx1 = (int)((ro >> 4) & 15u);
@@ -1336,7 +1348,8 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                 const int ce = min(ipr == 1 ? rx1 : min(cs + half - 1, rx1), A.img_w - 1 - (int)tx0);
                 const float pyf = ty0 + (float)row;
                 // diag 8: no pixel work
-                const bool rowok = item < total && (int)pyf < A.img_h && !(kDiag && (A.diag & 8));
+                // (the row inside the image, in integers: ty0 + row is exact)
+                const bool rowok = item < total && row < rows_in && !(kDiag && (A.diag & 8));
                 const float ex = G.x, eha = G.z, eb = G.w;
                 const float dy = G.y - pyf;
                 const float cq = (C.x * dy) * dy;  // splat_sigma_h's row terms
@@ -1353,13 +1366,16 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                 // walk the row by its v_out word (the planes at fixed LDS
                 // offsets) with dx stepping by -1 (exact: ex - px is exact or,
                 // far off, rounds alike); a lane without pixel work: no trip
-                const float *vp = &S.v[0][0] + row * kVRow + cs;
+                // (row * kVRow as a 24-bit multiply: full rate, where the 32-bit
+                // one the compiler picks runs at a quarter)
+                const int rword = __mul24(row, kVRow);
+                const float *vp = &S.v[0][0] + rword + cs;
                 // (diag 8 empties the range of every lane, the one at the planes' first
                 // word too, where vp - 1 lies below LDS address 0 and compares above
                 // vp: the walk would not end.  Without it a lane with no pixel work is
                 // past its entry's first row, or below the image.)
                 if (kDiag && (A.diag & 8)) vp = &S.v[0][0] + 1;
-                const float *const ve = rowok ? &S.v[0][0] + row * kVRow + ce : vp - 1;
+                const float *const ve = rowok ? &S.v[0][0] + rword + ce : vp - 1;
                 float dx = ex - (tx0 + (float)cs);
                 // kCut: the chunk's geometry is finite, so the alpha cut is the
                 // sigma threshold and alpha = vis (kSigmaCutBits); else the
@@ -1383,7 +1399,11 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                         // the same sums bit for bit, without the exec-mask
                         // bookkeeping per pixel -- bench.py 18.39k vs 18.21k it/s,
                         // tile kernel 45.5 vs 45.8 us, product libraries swapped on
-                        // one box, profiles/r06/select_cut/)
+                        // one box, profiles/r06/select_cut/).  This assumes a
+                        // finite v_out: 0 x inf would be NaN where a branch skips
+                        // the pixel.  v_out is norm x (clamped render - target)
+                        // or 0 (a NaN render fails the clamp's pass test), so it
+                        // is finite whenever the target frame is.
                         al = __float_as_uint(sgm) <= kSigmaCutBits ? vis : 0.0f;
                         const float v_alpha = fmaf(C.w, Pz, fmaf(C.z, Py, C.y * Px));
                         const float v_sigma = (-al) * v_alpha;
@@ -1416,11 +1436,22 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                 // spills, or 72 VGPRs at 7 waves per SIMD: 48.2;
                 // profiles/r06/tile_pairs/)
                 const float hdy = 0.5f * dy;
-                g[0] = rowok ? fmaf(2.0f * eha, s1, bdy * s0) : 0.0f;
-                g[1] = rowok ? fmaf(eb, s1, ((2.0f * C.x) * dy) * s0) : 0.0f;
-                g[2] = rowok ? 0.5f * s2 : 0.0f;
-                g[3] = rowok ? hdy * s1 : 0.0f;
-                g[4] = rowok ? (hdy * dy) * s0 : 0.0f;
+                g[0] = fmaf(2.0f * eha, s1, bdy * s0);
+                g[1] = fmaf(eb, s1, ((2.0f * C.x) * dy) * s0);
+                g[2] = 0.5f * s2;
+                g[3] = hdy * s1;
+                g[4] = (hdy * dy) * s0;
+                // A lane without pixel work made no trip: s0 = s1 = s2 = +0.
+                // Under the threshold cut the chunk's geometry is bounded, so
+                // the factors are finite and the five products are +-0 as they
+                // stand; a -0 only ever meets sums that started at +0 or are
+                // non-zero, which it leaves bit for bit as +0 would.  The other
+                // variant may hold an unbounded entry (inf x 0 = NaN): it
+                // keeps the selects.
+                if constexpr (!decltype(kcut)::value) {
+#pragma unroll
+                    for (int c = 0; c < 5; ++c) g[c] = rowok ? g[c] : 0.0f;
+                }
                 // segmented sums over the runs of items of one entry: the last item
                 // of an entry's run holds the run's sum (fixed tree order) and adds
                 // it to the entry's (a fixed order: rounds in sequence).  Measured
