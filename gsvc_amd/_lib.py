@@ -129,6 +129,7 @@ _SIGS = {
     "gsvc_quant_train_workspace_bytes": [_I],
     "gsvc_quant_train_step": [_P],
     "gsvc_quant_adan_step": [_P, _P, _P, _P],
+    "gsvc_quant_train_run": [_P],
 }
 # include/gsvc_amd_diag.h: the diagnostic library's extra entry points
 _DIAG_SIGS = {

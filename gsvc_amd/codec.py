@@ -345,7 +345,7 @@ def _encode(args) -> dict:
     res = compress_video(state, [by_index[i] for i in range(count)], K_frames=k_frames,
                          iterations=args.iterations, lr=args.lr, device=args.device,
                          delta_base=args.delta_base, seed=args.seed, entropy=args.entropy,
-                         fused=args.fused)
+                         fused=args.fused, run=args.run_length)
     size = write_video(args.out, res["streams"], fps=(args.fps_num, args.fps_den))
     return {"frames": count, "file_bytes": size, "k_frames": k_frames,
             "bpp": round(8.0 * sum(len(s) for s in res["streams"]) / (count * args.width * args.height), 6),
@@ -379,6 +379,8 @@ def main(argv=None) -> dict:
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--entropy", action="store_true", help="entropy-coded frame streams (version 2)")
     p.add_argument("--fused", action="store_true", help="the one-call training step (HIP devices)")
+    p.add_argument("--run", dest="run_length", type=int, default=None, metavar="K",
+                   help="with --fused: K iterations per call, the best state kept on the device")
     p.add_argument("--delta_base", choices=["overfit", "decoded"], default="decoded",
                    help="decoded (default): the file decodes to what training measured")
     p.add_argument("--fps_num", type=int, default=30)

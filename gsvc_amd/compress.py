@@ -82,6 +82,18 @@ class _QuantStepArgs(ctypes.Structure):
                 ("det_capacity", ctypes.c_longlong), ("stream", ctypes.c_void_p)]
 
 
+class _QuantRunArgs(ctypes.Structure):
+    """include/gsvc_amd.h gsvc_quant_train_run_args."""
+    _fields_ = [("step", ctypes.c_void_p), ("iterations", ctypes.c_int),
+                ("adan_hparams", ctypes.c_void_p), ("flags", ctypes.c_void_p),
+                ("loss_log", ctypes.c_void_p), ("best_mse", ctypes.c_void_p),
+                ("best_iter", ctypes.c_void_p), ("iter_base", ctypes.c_int),
+                ("best_xyz", ctypes.c_void_p), ("best_cholesky", ctypes.c_void_p),
+                ("best_features", ctypes.c_void_p), ("best_scale", ctypes.c_void_p),
+                ("best_beta", ctypes.c_void_p), ("best_codebooks", ctypes.c_void_p),
+                ("best_cluster_size", ctypes.c_void_p), ("best_embed_avg", ctypes.c_void_p)]
+
+
 _data_ptr = torch.Tensor.data_ptr
 
 
@@ -136,14 +148,20 @@ class BoundQuantStep:
         a.workspace, a.workspace_bytes = self.ws.data_ptr(), self.ws.numel()
         self.args_ref = ctypes.byref(a)
         self.fn = self.lib.gsvc_quant_train_step
+        # gsvc_quant_train_run: its arguments, and host arrays for run_cap iterations
+        self.run_args = _QuantRunArgs()
+        self.run_args.step = ctypes.addressof(a)
+        self.run_cap, self.run_host = 0, None
+        self.run_hp = self.run_flags = self.run_log = None
 
     def __del__(self):
-        if getattr(self, "host", None):
-            try:
-                self.lib.gsvc_host_free(self.host)
-            except Exception:  # interpreter shutdown
-                pass
-            self.host = None
+        for name in ("host", "run_host"):
+            if getattr(self, name, None):
+                try:
+                    self.lib.gsvc_host_free(getattr(self, name))
+                except Exception:  # interpreter shutdown
+                    pass
+                setattr(self, name, None)
 
     def __deepcopy__(self, memo):
         return None  # a copied model binds its own tensors on its first step
@@ -195,6 +213,136 @@ class BoundQuantStep:
             msg = self.lib.gsvc_last_error().decode(errors="replace")
             raise RuntimeError(f"gsvc_quant_train_step failed (status {rc}): {msg}")
         return tuple(self.host_f)
+
+    def _run_room(self, k: int) -> None:
+        """Host arrays for a run of ``k`` iterations: hyper-parameters, flags and
+        the pinned loss log (kept, and grown when a longer run comes)."""
+        if k <= self.run_cap:
+            return
+        host = self.lib.gsvc_host_alloc(16 * k)
+        if not host:
+            raise RuntimeError(self.lib.gsvc_last_error().decode(errors="replace"))
+        if self.run_host:
+            self.lib.gsvc_host_free(self.run_host)
+        self.run_host, self.run_cap = host, k
+        self.run_log = (ctypes.c_float * (4 * k)).from_address(host)
+        self.run_hp = (ctypes.c_double * (10 * k))()
+        self.run_flags = (ctypes.c_int * k)()
+        r = self.run_args
+        r.adan_hparams = ctypes.addressof(self.run_hp)
+        r.flags = ctypes.addressof(self.run_flags)
+        r.loss_log = host
+
+    def run(self, gt, rows, flags, best=None, iter_base=0):
+        """``gsvc_quant_train_run`` over ``len(rows)`` iterations: one call and
+        one wait; per iteration its four loss words.  ``rows[i]`` are iteration
+        i's ten hyper-parameters, ``flags[i]`` its flags; ``best`` the ten
+        device tensors of the best-state block (``QuantBestState``)."""
+        if not (gt.is_cuda and gt.dtype is torch.float32 and gt.is_contiguous()
+                and gt.numel() == 3 * self.H * self.W):
+            raise RuntimeError("gt must be a contiguous float32 CUDA tensor of 3*H*W elements")
+        k = len(rows)
+        self._run_room(k)
+        a, r = self.args, self.run_args
+        ws = T._workspace(self.dev, self.n, self.H, self.W)
+        if ws.pending is not None:  # a bound step's work enqueued ahead: not for this call
+            ws.dirty = True
+            ws = T._workspace(self.dev, self.n, self.H, self.W)
+        det = 0
+        if torch.are_deterministic_algorithms_enabled():
+            buf, cap = ws.det_workspace(self.dev, self.n, 16 * self.n)
+            a.det_workspace, a.det_workspace_bytes, a.det_capacity = buf.data_ptr(), buf.numel(), cap
+            det = T.TRAIN_DETERMINISTIC
+        else:
+            a.det_workspace, a.det_workspace_bytes, a.det_capacity = None, 0, 0
+        for i in range(k):
+            self.run_hp[10 * i:10 * i + 10] = rows[i]
+            self.run_flags[i] = flags[i] | det
+        a.gt = gt.data_ptr()
+        a.frame_index = ws.frame
+        a.flags = self.run_flags[0]
+        a.render_out = a.grads_out = None
+        a.train_workspace, a.train_workspace_bytes = ws.buf_ptr, ws.buf.numel()
+        stream = T._raw_stream(self.dev.index)
+        a.stream = stream
+        r.iterations = k
+        names = [f[0] for f in _QuantRunArgs._fields_]
+        if best is None:
+            for name in names[5:7] + names[8:]:
+                setattr(r, name, None)
+            r.iter_base = 0
+        else:
+            n = self.n
+            r.best_mse = T._f32_ptr(best[0], "best_mse", 1)
+            if best[1].dtype is not torch.int32 or best[1].numel() != 1 or not best[1].is_cuda:
+                raise RuntimeError("best_iter must be one int32 on the device")
+            r.best_iter = best[1].data_ptr()
+            for name, t, numel in zip(names[8:], best[2:], (2 * n, 3 * n, 3 * n, 3, 3, 48, 16, 48)):
+                setattr(r, name, T._f32_ptr(t, name, numel))
+            r.iter_base = iter_base
+        T._note_launch(a.xyz)
+        rc = self.lib.gsvc_quant_train_run(ctypes.byref(r))
+        if rc == 0:
+            ws.frame += k
+            rc = self.lib.gsvc_stream_sync(stream)
+        if rc != 0:
+            ws.dirty = True
+            msg = self.lib.gsvc_last_error().decode(errors="replace")
+            raise RuntimeError(f"gsvc_quant_train_run failed (status {rc}): {msg}")
+        words = list(self.run_log[:4 * k])
+        return [tuple(words[4 * i:4 * i + 4]) for i in range(k)]
+
+
+class QuantBestState:
+    """The reference's "best state" of a quantized fine-tune
+    (train_video_Compress.py:89-102), kept on the device by
+    ``train_run_quantize_fused``: snapshots of the eight tensors an iteration
+    changes (the three parameters, the Cholesky quantizer's scale and beta, the
+    codebooks with their moving averages), the best mean squared error and its
+    iteration.  It counts the iterations it has seen: an iteration's index is
+    global over the runs it was passed to."""
+
+    def __init__(self, model):
+        self.seen = 0
+        with torch.no_grad():
+            self.snapshot = [torch.empty_like(t) for t in self._tensors(model)]
+            dev = model._xyz.device
+            self.best_mse = torch.full((1,), math.inf, dtype=torch.float32, device=dev)
+            self.best_iter = torch.full((1,), -1, dtype=torch.int32, device=dev)
+
+    @staticmethod
+    def _tensors(model):
+        uq, vq = model.cholesky_quantizer, model.features_dc_quantizer
+        return [model._xyz, model._cholesky, model._features_dc, uq.scale, uq.beta, vq.codebooks,
+                vq.cluster_size, vq.embed_avg]
+
+    def tensors(self):
+        """What ``BoundQuantStep.run`` passes: the two scalars, the snapshots."""
+        return [self.best_mse, self.best_iter, *self.snapshot]
+
+    @property
+    def index(self) -> int:
+        """Global index of the best iteration; -1 when none has taken."""
+        return int(self.best_iter.item())
+
+    @property
+    def mse(self) -> float:
+        return float(self.best_mse.item())
+
+    def load_into(self, model) -> bool:
+        """Write the snapshot back into ``model``: its ``state_dict()`` is then
+        what the host loop's ``best_sd`` holds.  False, and nothing written,
+        when no iteration has taken."""
+        if self.index == -1:
+            return False
+        with torch.no_grad():
+            for dst, src in zip(self._tensors(model), self.snapshot):
+                if dst.shape != src.shape:
+                    raise ValueError("QuantBestState.load_into: the model's shapes differ from "
+                                     "the snapshot's")
+                dst.copy_(src)
+        T.bump_param_epoch()
+        return True
 
 
 class _QuantFrame(nn.Module):
@@ -383,10 +531,26 @@ class _QuantFrame(nn.Module):
         hook = grads_out is not None
         group = opt.param_groups[0]
         step = group.get("step", 0) + 1
+        hparams = self._fused_hparams(group, step)
+        state, flags = self._fused_state(params, step, hook)
+        bs, gt = self._fused_bound(params, state, gt_image)
+        if not hook:
+            group["step"] = step
+            T.bump_param_epoch()  # work another fused step enqueued ahead is stale now
+        return bs.step(gt, hparams, flags, render_out, grads_out)
+
+    @staticmethod
+    def _fused_hparams(group, step):
+        """The ten hyper-parameters of Adan step ``step`` at the group's learning rate."""
         b1, b2, b3 = group["betas"]
-        hparams = [b1, b2, b3, 1.0 - b1 ** step, 1.0 - b2 ** step, math.sqrt(1.0 - b3 ** step),
-                   group["lr"], group["weight_decay"], group["eps"], 1.0]
-        flags = 1 if group["no_prox"] else 0
+        return [b1, b2, b3, 1.0 - b1 ** step, 1.0 - b2 ** step, math.sqrt(1.0 - b3 ** step),
+                group["lr"], group["weight_decay"], group["eps"], 1.0]
+
+    def _fused_state(self, params, step, hook=False):
+        """The 20 Adan state tensors, created as ``Adan.step`` would, and the
+        flags of step ``step``: no_prox and the first-step bits."""
+        opt = self.optimizer
+        flags = 1 if opt.param_groups[0]["no_prox"] else 0
         state = []
         for q, p in enumerate(params):
             if hook:  # nothing is read or written: any valid pointers
@@ -401,6 +565,12 @@ class _QuantFrame(nn.Module):
                     st["neg_pre_grad"] = torch.zeros_like(p)
                 flags |= 1 << (1 + q)  # the kernel starts it at -grad
             state += [st["exp_avg"], st["exp_avg_sq"], st["exp_avg_diff"], st["neg_pre_grad"]]
+        return state, flags
+
+    def _fused_bound(self, params, state, gt_image):
+        """The ``BoundQuantStep`` of these tensors (rebuilt when one changed) and
+        the target as the entry takes it."""
+        vq = self.features_dc_quantizer
         gt = gt_image.detach() if gt_image.requires_grad else gt_image
         if gt.dtype is not torch.float32 or not gt.is_contiguous():
             gt = gt.float().contiguous()
@@ -412,10 +582,7 @@ class _QuantFrame(nn.Module):
                                 self.H, self.W, self.loss_type, vq, state)
             bs.loss_kind = T.LOSS_KIND[self.loss_type]
             self.__dict__["_bound_quant_step"] = bs
-        if not hook:
-            group["step"] = step
-            T.bump_param_epoch()  # work another fused step enqueued ahead is stale now
-        return bs.step(gt, hparams, flags, render_out, grads_out)
+        return bs, gt
 
     def train_iter_quantize_fused(self, gt_image):
         """``train_iter_quantize`` as one C call (``gsvc_quant_train_step``):
@@ -436,6 +603,52 @@ class _QuantFrame(nn.Module):
                              + vq.commitment_weight * (s0 + s1) / (3 * n))
         psnr = 10 * math.log10(1.0 / mse)
         return loss, psnr
+
+    def train_run_quantize_fused(self, gt_image, iterations, best=None):
+        """``iterations`` times ``train_iter_quantize_fused`` as ONE C call
+        (``gsvc_quant_train_run``) and one wait: returns (losses, psnrs), per
+        iteration what the single-step method returns (the loss as the float
+        its fp32 host tensor holds).  The hyper-parameter rows are made on the
+        host up front -- the learning rate of each iteration from the
+        scheduler, which steps ``iterations`` times -- and nothing in between
+        depends on a device result.  ``best`` (a ``QuantBestState``) keeps the
+        reference's best state on the device: iteration i of this run has the
+        index ``best.seen + i``.  Interleaves with ``train_iter_quantize_fused``
+        and ``train_iter_quantize`` at any iteration; the same restrictions,
+        raised before anything has changed."""
+        params = self._fused_tensors(gt_image)
+        k = int(iterations)
+        if k < 1:
+            raise ValueError(f"train_run_quantize_fused: iterations = {iterations}, not >= 1")
+        if best is not None and not isinstance(best, QuantBestState):
+            raise TypeError("train_run_quantize_fused: best must be a QuantBestState")
+        vq, opt = self.features_dc_quantizer, self.optimizer
+        if not vq.is_initted():
+            vq.init_codebooks(self._features_dc)
+        group = opt.param_groups[0]
+        step0 = group.get("step", 0)
+        state, first = self._fused_state(params, step0 + 1)
+        bs, gt = self._fused_bound(params, state, gt_image)
+        opt._opt_called = True  # keeps StepLR's call-order check quiet
+        self.scheduler.optimizer._opt_called = True
+        rows, flags = [], []
+        for i in range(k):
+            rows.append(self._fused_hparams(group, step0 + 1 + i))
+            flags.append(first if i == 0 else first & 1)
+            self.scheduler.step()
+        group["step"] = step0 + k
+        T._param_epoch[0] += k  # work another fused step enqueued ahead is stale now
+        base = 0 if best is None else best.seen
+        words = bs.run(gt, rows, flags, None if best is None else best.tensors(), base)
+        if best is not None:
+            best.seen += k
+        n = self._xyz.shape[0]
+        pick = 1 if self.loss_type == "L1" else 0
+        losses, psnrs = [], []
+        for w in words:
+            losses.append(float(np.float32(w[pick] + vq.commitment_weight * (w[2] + w[3]) / (3 * n))))
+            psnrs.append(10 * math.log10(1.0 / w[0]))
+        return losses, psnrs
 
 
 class GaussianVideoFrameQ(_QuantFrame):
@@ -693,7 +906,7 @@ def _load_overfit(model, cur: dict, prev: Optional[dict]) -> None:
 def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: Sequence[int] = (1,),
                    iterations: int = 30000, lr: float = 1e-3, device="cuda:0", loss_type="L2",
                    delta_base: str = "overfit", seed: Optional[int] = None, entropy: bool = False,
-                   segment: int = 32, fused: bool = False) -> dict:
+                   segment: int = 32, fused: bool = False, run: Optional[int] = None) -> dict:
     """Fine-tune every overfit frame model of ``state_dict`` (``frame_<i>`` ->
     {_xyz, _cholesky, _features_dc}, i from 1) under quantization against
     ``frames`` ([1,3,H,W] each) and encode it: frames listed in ``K_frames``
@@ -712,9 +925,18 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
     does.  With ``entropy`` the streams are entropy-coded (version 2, segments
     of ``segment`` splats) and "bpp_coded" gives their ``8 * len / (H * W)``.
     ``fused`` runs every iteration as ``train_iter_quantize_fused`` (one C call;
-    HIP devices and the L2 / L1 losses only -- anything else raises)."""
+    HIP devices and the L2 / L1 losses only -- anything else raises).  With
+    ``run=K`` (``fused`` only) a frame is trained in runs of K iterations, one
+    ``train_run_quantize_fused`` call each and a last shorter one, and the best
+    state is kept on the device (``QuantBestState``) instead of a host
+    comparison and a ``deepcopy`` per iteration: the same streams and states."""
     if delta_base not in ("overfit", "decoded"):
         raise ValueError("delta_base is 'overfit' or 'decoded'")
+    if run is not None:
+        if not fused:
+            raise ValueError("run= needs fused=True")
+        if int(run) < 1:
+            raise ValueError(f"run = {run}, not >= 1")
     if seed is not None:
         torch.manual_seed(seed)
     device = torch.device(device)
@@ -739,14 +961,21 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
         _load_overfit(model, cur, prev)
         model._init_data()
         model.train()
-        best_psnr, best_sd = -math.inf, None
-        train_iter = model.train_iter_quantize_fused if fused else model.train_iter_quantize
-        for _ in range(int(iterations)):
-            _, psnr = train_iter(gt)
-            if psnr > best_psnr:
-                best_psnr, best_sd = psnr, copy.deepcopy(model.state_dict())
-        if best_sd is not None:
-            model.load_state_dict(best_sd)
+        if run is not None:
+            best, left = QuantBestState(model), int(iterations)
+            while left > 0:
+                model.train_run_quantize_fused(gt, min(int(run), left), best)
+                left -= min(int(run), left)
+            best.load_into(model)
+        else:
+            best_psnr, best_sd = -math.inf, None
+            train_iter = model.train_iter_quantize_fused if fused else model.train_iter_quantize
+            for _ in range(int(iterations)):
+                _, psnr = train_iter(gt)
+                if psnr > best_psnr:
+                    best_psnr, best_sd = psnr, copy.deepcopy(model.state_dict())
+            if best_sd is not None:
+                model.load_state_dict(best_sd)
         model.eval()
         with torch.no_grad():
             out = model.forward_quantize()
@@ -775,7 +1004,7 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
     return out
 
 
-__all__ = ["GaussianVideoFrameQ", "GaussianVideoDelta", "Bits", "encode_frame", "encode_frames",
+__all__ = ["GaussianVideoFrameQ", "GaussianVideoDelta", "QuantBestState", "Bits", "encode_frame", "encode_frames",
            "decode_frames",
            "unpack_frames", "unpack_frames_host", "pack_planes_host", "parse_header",
            "compress_video", "HEADER_BYTES", "SPLAT_BYTES", "STREAM_MAGIC", "STREAM_VERSION",

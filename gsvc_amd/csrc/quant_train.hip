@@ -19,6 +19,10 @@
 //   quant_train_finish_kernel  one workgroup: the partials in block order,
 //       Adan on scale and beta, the codebooks' moving average, the loss words.
 //
+// gsvc_quant_train_run enqueues K such steps in one call (the same two
+// functions: quant_step_check, quant_step_enqueue) and, after each, the
+// keep-best kernel below: the best state of the fine-tune stays on the device.
+//
 // Reductions have a fixed order and no float atomics.  The 64 member values
 // (2 stages x 8 codewords x {count, 3-vector sum}): every lane leaves its
 // splat's (i0, i1, f, f - e0) in LDS; lane t of the block owns value
@@ -30,6 +34,8 @@
 // exact either way; the sums come out within half an ulp of the exact sum,
 // which is what holds embed_avg and the codebooks to the float64
 // restatement's bar.)
+#include <stdio.h>
+
 #include "adan.h"
 #include "frame.h"
 #include "quant_dev.h"
@@ -225,6 +231,7 @@ struct QuantTrainWs {
     float *xq, *Lq, *cq, *rec, *fwd_partials, *words, *partials;
     double *epart;
     unsigned char *codes_chol, *codes_rgb;
+    unsigned *ticket;  // gsvc_quant_train_run's keep-best kernel: its arrival count
     size_t bytes;
 };
 
@@ -248,6 +255,7 @@ static QuantTrainWs quant_train_ws(char *base, int num_points) {
     w.words = (float *)take(sizeof(float) * 4);  // commitment sums [2], render losses [2]
     w.codes_chol = (unsigned char *)take(3 * n);
     w.codes_rgb = (unsigned char *)take(2 * n);
+    w.ticket = (unsigned *)take(sizeof(unsigned));  // (last: the offsets above are the single step's)
     w.bytes = off;
     return w;
 }
@@ -342,6 +350,98 @@ static int quant_adan_launch(const gsvc_quant_train_args *a, const QuantTrainWs 
     return check_launch(what);
 }
 
+// gsvc_quant_train_run's keep-best kernel: the reference's "best state"
+// (train_video_Compress.py:89-102) without the host.  When this iteration's mse
+// is below *best_mse (strictly; false for a NaN) the eight tensors, as the
+// iteration left them, go to the snapshot, a grid-stride copy in 16-byte
+// chunks where both ends allow it and in floats otherwise (2 N and 3 N are no
+// multiples of 4 in general).  Every workgroup reads the pair once, through
+// its lane 0, BEFORE it arrives at the ticket; the workgroup that arrives last
+// -- after every read -- writes *best_mse and *best_iter, and the wrapping
+// increment leaves the ticket at zero for the next launch.  A launch that does
+// not take (the same decision in every workgroup: nothing has written the
+// pair) returns at once and leaves the ticket alone.
+constexpr int kKeepBlock = 256;
+constexpr int kKeepMaxBlocks = 256;  // a CU each
+constexpr int kKeepTensors = 8;
+static_assert(3 + 3 + 7 * kStages * kCodewords <= kKeepBlock, "a lane per small-tensor float");
+
+struct QuantKeepArgs {
+    long long len[kKeepTensors];  // 2 N, 3 N, 3 N, 3, 3, 48, 16, 48
+    const float *src[kKeepTensors];
+    float *dst[kKeepTensors];
+    const float *mse;  // the step's mean squared error (the word the finish kernel logs)
+    float *best_mse;
+    int *best_iter;
+    unsigned *ticket;
+    int iter;
+};
+
+__global__ __launch_bounds__(kKeepBlock) void quant_keep_best_kernel(QuantKeepArgs A) {
+    __shared__ float s_pair[2];
+    const int t = threadIdx.x;
+    if (t == 0) {
+        s_pair[0] = *A.mse;
+        s_pair[1] = *A.best_mse;
+    }
+    __syncthreads();
+    const float mse = s_pair[0];
+    // uniform over the grid: every workgroup reads the pair before any write to it (below).
+    // Without a take nothing is written and nobody needs to arrive.
+    if (!(mse < s_pair[1])) return;
+    const long long stride = (long long)gridDim.x * kKeepBlock;
+    const long long t0 = (long long)blockIdx.x * kKeepBlock + t;
+    // the three per-splat tensors: a pass loads a 16-byte chunk of each, then stores them
+    // (one round trip for the three); a tensor whose ends are not 16-byte aligned has no chunks
+    long long n4[3], most = 0;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const bool v4 = (((uintptr_t)A.dst[q] | (uintptr_t)A.src[q]) & 15u) == 0;
+        n4[q] = v4 ? A.len[q] >> 2 : 0;
+        most = n4[q] > most ? n4[q] : most;
+    }
+    for (long long i = t0; i < most; i += stride) {
+        // (named registers: an array under these conditions is lowered to LDS, a wait per load)
+        float4 c0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c1 = c0, c2 = c0;
+        if (i < n4[0]) c0 = reinterpret_cast<const float4 *>(A.src[0])[i];
+        if (i < n4[1]) c1 = reinterpret_cast<const float4 *>(A.src[1])[i];
+        if (i < n4[2]) c2 = reinterpret_cast<const float4 *>(A.src[2])[i];
+        if (i < n4[0]) reinterpret_cast<float4 *>(A.dst[0])[i] = c0;
+        if (i < n4[1]) reinterpret_cast<float4 *>(A.dst[1])[i] = c1;
+        if (i < n4[2]) reinterpret_cast<float4 *>(A.dst[2])[i] = c2;
+    }
+    // what the chunks leave (2 N and 3 N are no multiples of 4 in general), float by float
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+        for (long long i = 4 * n4[q] + t0; i < A.len[q]; i += stride) A.dst[q][i] = A.src[q][i];
+    // the five small tensors, 118 floats: a lane of the last workgroup each
+    if (blockIdx.x == gridDim.x - 1) {
+        int k = t;
+#pragma unroll
+        for (int q = 3; q < kKeepTensors; ++q) {
+            if (k >= 0 && k < (int)A.len[q]) A.dst[q][k] = A.src[q][k];
+            k -= (int)A.len[q];
+        }
+    }
+    if (t == 0) {
+        // lane 0's reads of the pair are done (the branch above took them); the fence keeps
+        // them ahead of the arrival, and the last arrival's writes behind every arrival
+        __threadfence();
+        const unsigned last = gridDim.x - 1;
+        if (atomicInc(A.ticket, last) == last) {
+            __threadfence();
+            *A.best_mse = mse;
+            *A.best_iter = A.iter;
+        }
+    }
+}
+
+static int blocks_of_keep(int n) {
+    const long long chunks = (8LL * n + 3) / 4;
+    const long long b = (chunks + kKeepBlock - 1) / kKeepBlock;
+    return (int)(b < 1 ? 1 : b > kKeepMaxBlocks ? kKeepMaxBlocks : b);
+}
+
 }  // namespace gsvc
 
 using namespace gsvc;
@@ -350,8 +450,8 @@ extern "C" size_t gsvc_quant_train_workspace_bytes(int num_points) {
     return quant_train_ws(nullptr, num_points).bytes;
 }
 
-extern "C" int gsvc_quant_train_step(const gsvc_quant_train_args *a) {
-    const char *what = "quant_train_step";
+// gsvc_quant_train_step's checks, all but the stream's
+static int quant_step_check(const gsvc_quant_train_args *a, const char *what) {
     int rc = quant_train_check(a, what);
     if (rc) return rc;
     if (!a->cholesky_bound) return set_error(GSVC_ERR_ARG, "%s: null cholesky_bound", what);
@@ -373,9 +473,14 @@ extern "C" int gsvc_quant_train_step(const gsvc_quant_train_args *a) {
                     gsvc_train_step_det_workspace_bytes(a->num_points, a->det_capacity)))
         return set_error(GSVC_ERR_WORKSPACE, "%s: GSVC_TRAIN_DETERMINISTIC needs a det_workspace of "
                                              "gsvc_train_step_det_workspace_bytes", what);
-    hipStream_t s = (hipStream_t)a->stream;
-    if ((rc = refuse_capture(s, what))) return rc;
+    return GSVC_OK;
+}
 
+// gsvc_quant_train_step's launches, on checked arguments
+static int quant_step_enqueue(const gsvc_quant_train_args *a, const char *what) {
+    hipStream_t s = (hipStream_t)a->stream;
+    const bool det = (a->flags & GSVC_TRAIN_DETERMINISTIC) != 0;
+    int rc;
     const QuantTrainWs w = quant_train_ws((char *)a->workspace, a->num_points);
     float *commit_sums = w.words, *render_loss = w.words + 2;
     // 1. the quantizer forward with its commitment sums
@@ -413,6 +518,94 @@ extern "C" int gsvc_quant_train_step(const gsvc_quant_train_args *a) {
     if (rc) return rc;
     // 3, 4. the quantizer's backward, Adan, the codebooks' moving average, the loss words
     return quant_adan_launch(a, w, w.rec, w.codes_rgb, render_loss, commit_sums, what);
+}
+
+extern "C" int gsvc_quant_train_step(const gsvc_quant_train_args *a) {
+    const char *what = "quant_train_step";
+    int rc = quant_step_check(a, what);
+    if (rc) return rc;
+    if ((rc = refuse_capture((hipStream_t)a->stream, what))) return rc;
+    return quant_step_enqueue(a, what);
+}
+
+// a failed launch of iteration i: the status, with the iteration ahead of the message
+static int run_error(int rc, int i) {
+    char msg[384];
+    snprintf(msg, sizeof msg, "%s", gsvc_last_error());
+    return set_error(rc, "quant_train_run: iteration %d: %s", i, msg);
+}
+
+extern "C" int gsvc_quant_train_run(const gsvc_quant_train_run_args *r) {
+    const char *what = "quant_train_run";
+    if (!r) return set_error(GSVC_ERR_ARG, "%s: null run arguments", what);
+    if (!r->step) return set_error(GSVC_ERR_ARG, "%s: null step arguments", what);
+    if (r->iterations < 1) return set_error(GSVC_ERR_ARG, "%s: iterations < 1", what);
+    if (!r->adan_hparams) return set_error(GSVC_ERR_ARG, "%s: null adan_hparams [iterations][10]", what);
+    if (!r->flags) return set_error(GSVC_ERR_ARG, "%s: null flags [iterations]", what);
+    if (!r->loss_log) return set_error(GSVC_ERR_ARG, "%s: null loss_log [iterations][4]", what);
+    float *const snap[kKeepTensors] = {r->best_xyz,   r->best_cholesky,  r->best_features,
+                                       r->best_scale, r->best_beta,      r->best_codebooks,
+                                       r->best_cluster_size, r->best_embed_avg};
+    int set = (r->best_mse != nullptr) + (r->best_iter != nullptr);
+    for (int q = 0; q < kKeepTensors; ++q) set += snap[q] != nullptr;
+    if (set != 0 && set != kKeepTensors + 2)
+        return set_error(GSVC_ERR_ARG, "%s: best_mse, best_iter and the eight snapshot buffers go "
+                                       "together", what);
+    const bool keep = set != 0;
+    if (r->step->grads_out)
+        return set_error(GSVC_ERR_ARG, "%s: grads_out is set; a run has no test-hook mode", what);
+    const int K = r->iterations;
+    for (int i = 1; i < K; ++i)
+        if ((r->flags[i] ^ r->flags[0]) & GSVC_TRAIN_DETERMINISTIC)
+            return set_error(GSVC_ERR_ARG, "%s: GSVC_TRAIN_DETERMINISTIC differs between iterations "
+                                           "0 and %d", what, i);
+    // the single step's checks, for every iteration's flags (the other fields do not change)
+    gsvc_quant_train_args a = *r->step;
+    for (int i = 0; i < K; ++i) {
+        a.adan_hparams = r->adan_hparams + 10 * (size_t)i;
+        a.flags = r->flags[i];
+        a.loss = r->loss_log + 4 * (size_t)i;
+        const int rc = quant_step_check(&a, what);
+        if (rc) return rc;
+    }
+    hipStream_t s = (hipStream_t)a.stream;
+    int rc = refuse_capture(s, what);
+    if (rc) return rc;
+
+    const QuantTrainWs w = quant_train_ws((char *)a.workspace, a.num_points);
+    QuantKeepArgs B{};
+    int keep_blocks = 0;
+    if (keep) {
+        const long long n = a.num_points;
+        const long long len[kKeepTensors] = {2 * n, 3 * n, 3 * n, 3, 3, kStages * kCodewords * 3,
+                                             kStages * kCodewords, kStages * kCodewords * 3};
+        const float *const src[kKeepTensors] = {a.xyz,  a.cholesky,  a.features,     a.scale,
+                                                a.beta, a.codebooks, a.cluster_size, a.embed_avg};
+        for (int q = 0; q < kKeepTensors; ++q) {
+            B.len[q] = len[q];
+            B.src[q] = src[q];
+            B.dst[q] = snap[q];
+        }
+        B.mse = w.words + 2;  // the render step's {mse, mae}: loss_log[4 i] is a copy of this word
+        B.best_mse = r->best_mse;
+        B.best_iter = r->best_iter;
+        B.ticket = w.ticket;
+        keep_blocks = blocks_of_keep(a.num_points);
+        if ((rc = dev_zero(w.ticket, sizeof(unsigned), s))) return run_error(rc, 0);
+    }
+    for (int i = 0; i < K; ++i) {
+        a.adan_hparams = r->adan_hparams + 10 * (size_t)i;
+        a.flags = r->flags[i];
+        a.loss = r->loss_log + 4 * (size_t)i;
+        a.frame_index = r->step->frame_index + i;
+        if ((rc = quant_step_enqueue(&a, what))) return run_error(rc, i);
+        if (keep) {
+            B.iter = r->iter_base + i;
+            hipLaunchKernelGGL(quant_keep_best_kernel, dim3(keep_blocks), dim3(kKeepBlock), 0, s, B);
+            if ((rc = check_launch(what))) return run_error(rc, i);
+        }
+    }
+    return GSVC_OK;
 }
 
 extern "C" int gsvc_quant_adan_step(const gsvc_quant_train_args *a, const float *grad_records,

@@ -55,8 +55,8 @@ enum gsvc_status {
  * library (gsvc_amd_diag.h); GSVC_ERR_CAPTURE added.
  * ABI version 3: gsvc_encode_stream_bytes / gsvc_encode_stream added.
  * ABI version 4: gsvc_quant_train_workspace_bytes / gsvc_quant_train_step /
- * gsvc_quant_adan_step added.  gsvc_rgb_to_i420 joined version 4 later: an
- * added entry, nothing existing changed. */
+ * gsvc_quant_adan_step added.  gsvc_rgb_to_i420 and gsvc_quant_train_run joined
+ * version 4 later: added entries, nothing existing changed. */
 #define GSVC_ABI_VERSION 4
 
 /* Library identity and error reporting. */
@@ -922,6 +922,61 @@ int gsvc_quant_train_step(const gsvc_quant_train_args *args);
  * device memory; zeros without). */
 int gsvc_quant_adan_step(const gsvc_quant_train_args *args, const float *grad_records,
                          const unsigned char *codes_rgb, const float *commit_sums);
+
+/* ``iterations`` (K >= 1) fused quantized training steps in one call, with no
+ * host round trip in between, and the reference's "best state"
+ * (train_video_Compress.py:89-102) kept on the device.  On step->stream the
+ * call enqueues, for i = 0 .. K-1, exactly the launches of
+ * gsvc_quant_train_step(step) with
+ *   adan_hparams = run->adan_hparams + 10 i   (host array [K][10]),
+ *   flags        = run->flags[i]              (host array [K]: no_prox, the
+ *                  first-step bits; GSVC_TRAIN_DETERMINISTIC must be equal in
+ *                  all K entries),
+ *   frame_index  = step->frame_index + i      (the train workspace's parity),
+ *   loss         = run->loss_log + 4 i        ([K][4], device or coherent host
+ *                  memory; read it after gsvc_stream_sync).
+ * step's own adan_hparams, flags and loss are not read.  step->grads_out must
+ * be NULL: a run has no test-hook mode.
+ *
+ * The best-state block is best_mse, best_iter and the eight snapshot buffers
+ * best_xyz [N,2], best_cholesky [N,3], best_features [N,3], best_scale [3],
+ * best_beta [3], best_codebooks [2,8,3], best_cluster_size [2,8],
+ * best_embed_avg [2,8,3] (device memory, 4-byte aligned, not overlapping the
+ * step's tensors): every pointer set, or every pointer NULL -- they go
+ * together.  When it is set, the keep-best kernel follows each iteration's
+ * launches: with mse the float that loss_log[4 i] receives, and only when
+ * mse < *best_mse (strict: the first of equal values stays; a NaN never
+ * takes), it copies the eight tensors AS THE ITERATION LEFT THEM (after the
+ * update) into the snapshot and sets *best_mse = mse, *best_iter = iter_base +
+ * i.  This is the reference's rule: the PSNR of iteration i belongs to the
+ * state before its update, the state saved is the one after it, and mse < best
+ * is psnr > best_psnr for psnr = 10 log10(1 / mse).  *best_mse (start it at
+ * +inf) and *best_iter (start it at -1) carry from call to call; iter_base is
+ * the global index of this call's iteration 0.  Every workgroup of the kernel
+ * decides from the same (mse, *best_mse): the two words are written by the
+ * workgroup that arrives last at a ticket in ``workspace`` (zeroed by one
+ * small launch at the head of the call).  Without the block nothing beyond the
+ * K steps is enqueued.
+ *
+ * Everything -- the step's arguments as by gsvc_quant_train_step, the run's
+ * own, all K flag words -- is validated before the first launch; a capturing
+ * stream is refused (GSVC_ERR_CAPTURE).  A launch error at iteration i returns
+ * at once, with the iteration in gsvc_last_error(); the iterations before it
+ * stay enqueued.  Not part of the reference. */
+typedef struct gsvc_quant_train_run_args {
+    const gsvc_quant_train_args *step;
+    int iterations;
+    const double *adan_hparams;
+    const int *flags;
+    float *loss_log;
+    float *best_mse;
+    int *best_iter;
+    int iter_base;
+    float *best_xyz, *best_cholesky, *best_features;
+    float *best_scale, *best_beta;
+    float *best_codebooks, *best_cluster_size, *best_embed_avg;
+} gsvc_quant_train_run_args;
+int gsvc_quant_train_run(const gsvc_quant_train_run_args *run);
 
 #ifdef __cplusplus
 }
