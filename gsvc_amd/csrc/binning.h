@@ -14,7 +14,9 @@ namespace gsvc {
 // tile_cap > 0 (with ids_sorted): each tile keeps at most tile_cap entries --
 // the first tile_cap by splat id; a tile with more has its list rebuilt from
 // the splats' bboxes in id order (tile_ids.h wave_brute_ids); capacity need
-// only cover sum(min(count, tile_cap)).
+// only cover sum(min(count, tile_cap)).  Fill, segment sort and rebuild all
+// skip what would land at or past capacity (a tile whose segment ends past it
+// is neither sorted nor rebuilt): meta[1] = 1 and no write past the capacity.
 int tile_bins_from_counts(int num_points, const float2 *xys, const int *radii, int tbx, int tby,
                           long long capacity, unsigned *counts, unsigned *cursor, int *ids_scratch,
                           int *ids_sorted, int2 *bins, int *meta, bool zero_counts,

@@ -511,14 +511,18 @@ __global__ __launch_bounds__(64) void tile_segsort_kernel(int ntiles, const int2
 // tile_cap mode: a tile with more than tile_cap entries kept an arbitrary
 // tile_cap of them; its first tile_cap ids are rebuilt in id order by one
 // wave scanning every splat's bbox (rare: trained frames' densest tiles).
+// A tile whose segment ends past ``capacity`` is skipped, as in the segment
+// sort: meta[1] reports it and nothing is written at or past the capacity.
 __global__ __launch_bounds__(64) void tile_overflow_kernel(int n, const float2 *__restrict__ xys,
                                                            const int *__restrict__ radii, int tbx,
                                                            int tby, const unsigned *__restrict__ counts,
                                                            const int2 *__restrict__ bins,
-                                                           int *__restrict__ ids_out, unsigned tile_cap) {
+                                                           int *__restrict__ ids_out, unsigned tile_cap,
+                                                           long long capacity) {
     const int tile = blockIdx.x;
     if (counts[tile] <= tile_cap) return;
     const int2 range = bins[tile];
+    if ((long long)range.y > capacity) return;
     wave_brute_ids(xys, radii, 0, n, tbx, tby, tile, ids_out + range.x);
 }
 
@@ -621,7 +625,7 @@ int tile_bins_from_counts(int num_points, const float2 *xys, const int *radii, i
         if (tile_cap)
             hipLaunchKernelGGL(tile_overflow_kernel, dim3(ntiles), dim3(64), 0, s, num_points, xys,
                                radii, tbx, tby, (const unsigned *)counts, (const int2 *)bins,
-                               ids_sorted, tile_cap);
+                               ids_sorted, tile_cap, capacity);
     }
     return check_launch("tile binning");
 }

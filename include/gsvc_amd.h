@@ -237,7 +237,9 @@ int gsvc_bin_and_sort_tiles(
  * the reference's sorted pairs and tile_bins[tbx*tby] ([start,end), (0,0)
  * when empty), every size staying on the device.  meta[0] <- M,
  * meta[1] <- 1 if the entries kept exceed capacity (outputs then
- * incomplete).  ids_scratch and gaussian_ids_sorted hold >= capacity ints.
+ * incomplete: a tile whose segment ends past capacity is neither sorted nor,
+ * with tile_cap, rebuilt; no element at or past capacity is written).
+ * ids_scratch and gaussian_ids_sorted hold >= capacity ints.
  * tile_cap > 0 keeps only each tile's first tile_cap entries in id order (the
  * sum rasterizer reads no more than 256 per tile, forward.cu:569-571,613; a
  * tile with more is rebuilt from the splats' bboxes in id order), so
