@@ -2,9 +2,11 @@
 
 ``compress.encode_frame`` gives one byte string per frame; this module puts a
 video's frame streams into ONE file with an index (``write_video`` /
-``read_video``), decodes such a file -- or a list of streams -- to planar 8-bit
-I420 in batches on the GPU (``decode_video``: ``decode_frames(output="i420")``,
-csrc/yuv_out.hip), and is the command line of the three steps:
+``read_video``), decodes such a file -- or a list of streams -- to planar YUV
+4:2:0 (8-bit I420 by default; 8 to 16 bits, BT.601 or BT.709, limited or full
+range: ``video.YuvFormat``) in batches on the GPU (``decode_video``:
+``decode_frames(output="i420")``, csrc/yuv_out.hip and csrc/yuv_fmt.hip), and
+is the command line of the three steps:
 
     python -m gsvc_amd.codec encode MODELS.pth SRC.yuv OUT.gsvf --width W --height H
     python -m gsvc_amd.codec info OUT.gsvf
@@ -16,8 +18,13 @@ Not part of the reference, which writes PNG images and an MP4 through OpenCV
 The container, little-endian:
 
     bytes 0-63      "GSVF", u32 version 1, u32 H, u32 W, u32 num_frames,
-                    u32 fps_num, u32 fps_den, u32 flags 0, u64 index_offset,
-                    u64 file_bytes, zero to 64
+                    u32 fps_num, u32 fps_den, u32 flags, u64 index_offset,
+                    u64 file_bytes, zero to 64; flags: the source's pixel
+                    format (video.YuvFormat): bits 0-1 depth (0: 8, 1: 10,
+                    2: 12, 3: 16 bits), bit 4 matrix (0 bt601, 1 bt709),
+                    bit 6 full range, every other bit 0 (files written
+                    before the format existed have flags 0: 8-bit BT.601
+                    limited range)
     64 ...          the frame streams of encode_frame (version 1 or 2, any
                     mix), back to back
     index_offset... per frame: u64 offset, u32 length, u32 flags (bit 0: delta,
@@ -41,6 +48,7 @@ import numpy as np
 import torch
 
 from .compress import FLAG_DELTA, HEADER_BYTES, decode_frames, parse_header
+from .video import YuvFormat, add_format_arguments, format_of_arguments
 
 FILE_MAGIC = b"GSVF"
 FILE_VERSION = 1
@@ -79,8 +87,10 @@ class Video:
     from 0), ``frame(i)`` (the stream's bytes), ``span(i)`` (the frames a
     decoder needs for frame i: from the last key frame <= i to i)."""
 
-    def __init__(self, streams: Sequence[bytes], heads: Sequence[dict], fps=(30, 1), file_bytes: int = 0):
+    def __init__(self, streams: Sequence[bytes], heads: Sequence[dict], fps=(30, 1), file_bytes: int = 0,
+                 fmt: Optional[YuvFormat] = None):
         self._streams = streams
+        self.format = fmt or YuvFormat()  # the source's pixel format (the header's flags)
         self.H, self.W = int(heads[0]["H"]), int(heads[0]["W"])
         self.num_frames = len(streams)
         self.fps = (int(fps[0]), int(fps[1]))
@@ -107,10 +117,13 @@ def _video_of_streams(streams: Sequence[bytes]) -> Video:
     return Video(streams, heads)
 
 
-def write_video(path, streams: Sequence[bytes], fps=(30, 1)) -> int:
+def write_video(path, streams: Sequence[bytes], fps=(30, 1), fmt: Optional[YuvFormat] = None) -> int:
     """Write the frame streams (``encode_frame``, either version) as one file;
-    returns its size.  The streams are checked as ``read_video`` will."""
+    returns its size.  The streams are checked as ``read_video`` will.  ``fmt``:
+    the source's pixel format, kept in the header's flags (None: the legacy
+    format, flags 0)."""
     vid = _video_of_streams(streams)
+    flags = (fmt or YuvFormat()).flags
     fps_num, fps_den = int(fps[0]), int(fps[1])
     if fps_num <= 0 or fps_den <= 0:
         raise ValueError("fps is (numerator, denominator), both positive")
@@ -121,7 +134,7 @@ def write_video(path, streams: Sequence[bytes], fps=(30, 1)) -> int:
         off += len(s)
     index_offset = off
     file_bytes = index_offset + INDEX_ENTRY_BYTES * vid.num_frames
-    head = _FILE_HEADER.pack(FILE_MAGIC, FILE_VERSION, vid.H, vid.W, vid.num_frames, fps_num, fps_den, 0,
+    head = _FILE_HEADER.pack(FILE_MAGIC, FILE_VERSION, vid.H, vid.W, vid.num_frames, fps_num, fps_den, flags,
                              index_offset, file_bytes)
     with open(path, "wb") as fh:
         fh.write(head + bytes(FILE_HEADER_BYTES - len(head)))
@@ -148,7 +161,8 @@ def read_video(path) -> Video:
         raise ValueError(f"wrong magic {magic!r}, not {FILE_MAGIC!r}")
     if version != FILE_VERSION:
         raise ValueError(f"file version {version}, not {FILE_VERSION}")
-    if flags != 0 or any(blob[_FILE_HEADER.size:FILE_HEADER_BYTES]):
+    fmt = YuvFormat.from_flags(flags)  # ValueError("unknown file flags ...") for an undefined bit
+    if any(blob[_FILE_HEADER.size:FILE_HEADER_BYTES]):
         raise ValueError("unknown file flags or non-zero reserved header bytes")
     if file_bytes != len(blob):
         raise ValueError(f"file_bytes = {file_bytes}, the file has {len(blob)} (truncated or padded)")
@@ -184,18 +198,22 @@ def read_video(path) -> Video:
         streams.append(s)
         heads.append(h)
     _check_sequence(heads, H, W)
-    return Video(streams, heads, (fps_num, fps_den), file_bytes)
+    return Video(streams, heads, (fps_num, fps_den), file_bytes, fmt)
 
 
-def _psnr(sse: int, count: int) -> float:
-    return math.inf if sse == 0 else 10.0 * math.log10(255.0 * 255.0 * count / sse)
+def _psnr(sse: int, count: int, peak: int = 255) -> float:
+    return math.inf if sse == 0 else 10.0 * math.log10(float(peak) * float(peak) * count / sse)
 
 
 def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Optional[range] = None,
-                 reference=None) -> dict:
+                 reference=None, fmt: Optional[YuvFormat] = None) -> dict:
     """Decode a container file (a path) or a list of frame streams to planar
-    8-bit I420, appended frame by frame to ``out_path`` (a raw .yuv; nothing
-    is written when None).
+    YUV 4:2:0, appended frame by frame to ``out_path`` (a raw .yuv; nothing
+    is written when None).  ``fmt``: the output's pixel format; None means the
+    file's own (``Video.format``: the source's; 8-bit I420, BT.601 limited
+    range for a stream list and for files written before the header carried
+    one).  Any other value re-targets the output -- the models are float, so
+    any depth can be written -- and ``reference`` is read in that format.
 
     Frames are decoded in batches of at most ``batch``: one
     ``decode_frames(output="i420")`` call each, the decoded parameters of a
@@ -208,8 +226,8 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
 
     ``frames=range(a, b)`` decodes from the key frame of ``span(a)`` and
     discards what precedes ``a``.  ``reference``: the source .yuv; adds
-    per-frame ``psnr_y / psnr_u / psnr_v`` (8-bit, from the kernel's exact
-    integer SSE, float64 on the host; inf for identical planes) and
+    per-frame ``psnr_y / psnr_u / psnr_v`` (peak 2^bit_depth - 1, from the kernel's
+    exact integer SSE, float64 on the host; inf for identical planes) and
     ``psnr_yuv`` = (6 Y + U + V) / 8.  Returns {"frames", "bytes_written",
     "seconds" (host clock, ending in a synchronise), and the PSNR lists}."""
     vid = read_video(src) if isinstance(src, (str, os.PathLike)) else _video_of_streams(src)
@@ -223,7 +241,8 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
     H, W = vid.H, vid.W
     if H % 2 or W % 2:
         raise ValueError(f"I420 needs an even height and width, not {H}x{W}")
-    size = H * W * 3 // 2
+    fmt = fmt or vid.format
+    size = fmt.frame_bytes(H, W)
     mm = None
     if reference is not None:
         mm = np.memmap(reference, dtype=np.uint8, mode="r")
@@ -264,7 +283,7 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
             if mm is not None:
                 ref = torch.from_numpy(np.array(mm[s * size:e * size])).to(device)
             out, state = decode_frames(streams, device, prev=state, return_state=True, output="i420",
-                                       reference=ref)
+                                       reference=ref, fmt=fmt)
             sse = None
             if ref is not None:
                 out, sse = out
@@ -299,9 +318,9 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
     if mm is not None:
         tot = np.concatenate(sse_rows).astype(np.int64)
         n, cn = H * W, H * W // 4
-        res["psnr_y"] = [_psnr(int(r[0]), n) for r in tot]
-        res["psnr_u"] = [_psnr(int(r[1]), cn) for r in tot]
-        res["psnr_v"] = [_psnr(int(r[2]), cn) for r in tot]
+        res["psnr_y"] = [_psnr(int(r[0]), n, fmt.peak) for r in tot]
+        res["psnr_u"] = [_psnr(int(r[1]), cn, fmt.peak) for r in tot]
+        res["psnr_v"] = [_psnr(int(r[2]), cn, fmt.peak) for r in tot]
         res["psnr_yuv"] = [(6.0 * y + u + v) / 8.0
                            for y, u, v in zip(res["psnr_y"], res["psnr_u"], res["psnr_v"])]
     return res
@@ -319,6 +338,8 @@ def _info(args) -> dict:
     streams = sum(len(vid.frame(i)) for i in range(vid.num_frames))
     return {"H": vid.H, "W": vid.W, "frames": vid.num_frames, "fps": list(vid.fps),
             "key_frames": vid.key_frames, "file_bytes": vid.file_bytes,
+            "format": {"bit_depth": vid.format.bit_depth, "matrix": vid.format.matrix,
+                       "full_range": vid.format.full_range},
             "bpp": round(8.0 * streams / (vid.num_frames * vid.H * vid.W), 6),
             "splats": vid.sizes, "entropy_coded": sum(v == 2 for v in vid.versions)}
 
@@ -328,8 +349,11 @@ def _decode(args) -> dict:
     if args.frames:
         lo, _, hi = args.frames.partition(":")
         frames = range(int(lo or 0), int(hi) if hi else read_video(args.file).num_frames)
+    fmt = format_of_arguments(args)  # an override: on top of the file's own format
+    if fmt is not None:
+        fmt = format_of_arguments(args, read_video(args.file).format)
     return decode_video(args.file, args.out, device=args.device, batch=args.batch, frames=frames,
-                        reference=args.reference)
+                        reference=args.reference, fmt=fmt)
 
 
 def _encode(args) -> dict:
@@ -337,8 +361,9 @@ def _encode(args) -> dict:
     from .video import load_yuv_frames
     state = torch.load(args.models, map_location="cpu")
     count = sum(1 for k in state if k.startswith("frame_"))
+    fmt = format_of_arguments(args)
     by_index, total = load_yuv_frames(args.src, args.width, args.height, torch.device(args.device),
-                                      range(count))
+                                      range(count), fmt=fmt)
     if total < count:
         raise ValueError(f"{args.models} holds {count} frame models, {args.src} {total} frames")
     k_frames = sorted({1} | {int(x) for x in args.k_frames.split(",") if x.strip()})
@@ -346,7 +371,7 @@ def _encode(args) -> dict:
                          iterations=args.iterations, lr=args.lr, device=args.device,
                          delta_base=args.delta_base, seed=args.seed, entropy=args.entropy,
                          fused=args.fused, run=args.run_length)
-    size = write_video(args.out, res["streams"], fps=(args.fps_num, args.fps_den))
+    size = write_video(args.out, res["streams"], fps=(args.fps_num, args.fps_den), fmt=fmt)
     return {"frames": count, "file_bytes": size, "k_frames": k_frames,
             "bpp": round(8.0 * sum(len(s) for s in res["streams"]) / (count * args.width * args.height), 6),
             "psnr": [round(p, 4) for p in res["psnr"]]}
@@ -365,11 +390,12 @@ def main(argv=None) -> dict:
     p.add_argument("--device", default=_default_device())
     p.add_argument("--batch", type=int, default=8)
     p.add_argument("--frames", default=None, help="A:B, frames A <= i < B from 0 (default all)")
-    p.add_argument("--reference", default=None, help="the source .yuv: per-frame 8-bit PSNR")
+    p.add_argument("--reference", default=None, help="the source .yuv, in the output's format: per-frame PSNR")
+    add_format_arguments(p)  # override the file's own format
     p.set_defaults(run=_decode)
     p = sub.add_parser("encode", help="overfit frame models + source .yuv -> container file")
     p.add_argument("models", help="gmodels_state_dict.pth of gsvc_amd.video (frame_<n> from 1)")
-    p.add_argument("src", help="the source video, planar I420")
+    p.add_argument("src", help="the source video, planar YUV 4:2:0")
     p.add_argument("out")
     p.add_argument("--width", type=int, required=True)
     p.add_argument("--height", type=int, required=True)
@@ -385,6 +411,7 @@ def main(argv=None) -> dict:
                    help="decoded (default): the file decodes to what training measured")
     p.add_argument("--fps_num", type=int, default=30)
     p.add_argument("--fps_den", type=int, default=1)
+    add_format_arguments(p)  # of src; stored in the file
     p.add_argument("--device", default=_default_device())
     p.set_defaults(run=_encode)
     args = ap.parse_args(argv)

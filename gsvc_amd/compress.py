@@ -832,11 +832,13 @@ def unpack_frames(streams: Sequence[bytes], device, cholesky_bound=None, prev=No
 
 
 def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: bool = False,
-                  output: str = "rgb", reference=None):
+                  output: str = "rgb", reference=None, fmt=None):
     """Frame streams (``encode_frame``, either version, in any mix) to images
-    [F, 3, H, W], or with ``output="i420"`` to 8-bit planar I420 frames, uint8
-    [F, H*W*3/2] (``video.rgb_to_i420`` of those images; with ``reference``,
-    the source's I420 frames, the pair (frames, int64 [F, 3] squared error)).
+    [F, 3, H, W], or with ``output="i420"`` to planar 4:2:0 frames, uint8
+    [F, fmt.frame_bytes(H, W)] (``video.rgb_to_i420`` of those images in the
+    pixel format ``fmt``, a ``video.YuvFormat``; None: 8-bit I420, BT.601
+    limited range; with ``reference``, the source's frames in that format,
+    the pair (frames, int64 [F, 3] squared error)).
 
     On a HIP device: one unpack launch for all frames, then
     ``render_frames_sum``.  A delta frame adds the DECODED parameters of the
@@ -848,6 +850,8 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
         raise ValueError(f"decode_frames: output is 'rgb' or 'i420', not {output!r}")
     if reference is not None and output != "i420":
         raise ValueError("decode_frames: reference frames are compared in I420 (output='i420')")
+    if fmt is not None and output != "i420":
+        raise ValueError("decode_frames: a pixel format applies to output='i420'")
     if len(streams) == 0:
         raise ValueError("decode_frames: no frames")
     if device.type == "cuda":
@@ -876,7 +880,7 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
         state = tuple(torch.from_numpy(np.ascontiguousarray(t)) for t in (xq, Lpre, cq))
     if output == "i420":
         from .video import rgb_to_i420
-        imgs = rgb_to_i420(imgs, reference)
+        imgs = rgb_to_i420(imgs, reference, fmt)
     return (imgs, state) if return_state else imgs
 
 

@@ -4,9 +4,11 @@ A restatement of train_video_Represent.py (reference :17-401) and the helpers
 it uses from utils.py (process_yuv_video :134-156, EarlyStopping :188-211,
 detect_outliers_mean_diff :214-229) that runs on the MI355X path:
 
-* frames come from a planar I420 file (converted on the GPU by
-  ``gsvc_i420_to_rgb``, OpenCV's BT.601 arithmetic) or from a seeded synthetic
-  video (the UVG sequences are not in this image);
+* frames come from a planar YUV 4:2:0 file (converted on the GPU: 8-bit I420
+  by ``gsvc_i420_to_rgb``, OpenCV's BT.601 arithmetic; 10, 12 and 16 bits,
+  BT.709 and full range by ``gsvc_yuv420_to_rgb``, ``--bit_depth --matrix
+  --full_range``) or from a seeded synthetic video (the UVG sequences are not
+  in this image);
 * K-frames (key frames, trained from scratch) come from
   ``<savdir>/<data>/K_frames.txt`` when present, else from the reference's
   detector (500 scratch iterations and a 100-iteration P-probe per frame,
@@ -37,6 +39,8 @@ frames whose smaller side is <= 160 (where ms_ssim asserts) report NaN.
 from __future__ import annotations
 
 import argparse
+import ctypes
+import dataclasses
 import json
 import math
 import os
@@ -56,12 +60,165 @@ from .shard import aggregate_video_metrics, forced_k_frames, gops, shard_gops
 # frames
 
 
-def i420_to_rgb(yuv: torch.Tensor, height: int, width: int) -> torch.Tensor:
-    """One I420 frame (uint8 device tensor) -> [1, 3, H, W] float RGB in [0, 1]
-    (cv2.cvtColor(COLOR_YUV2RGB_I420) + ToTensor) on the GPU.  A uint8 CPU
-    tensor takes the kernel's arithmetic in torch integer ops (the codec's
-    encoder on a host without a GPU)."""
+_DEPTHS = (8, 10, 12, 16)       # the container's depth codes 0..3
+_MATRICES = ("bt601", "bt709")  # (Kr, Kb) below; the container's matrix bit
+_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+_FLAG_DEPTH, _FLAG_MATRIX, _FLAG_FULL = 0x3, 0x10, 0x40
+
+
+@dataclasses.dataclass(frozen=True)
+class YuvFormat:
+    """A planar YUV 4:2:0 pixel format: ``bit_depth`` 8, 10, 12 or 16 (above 8
+    bits: 16-bit little-endian samples, the value in the low bits, as
+    yuv420p10le), ``matrix`` "bt601" or "bt709", limited or full range.
+    ``YuvFormat()`` is the legacy format (8-bit BT.601 limited range), which
+    keeps OpenCV's arithmetic (csrc/yuv.hip, csrc/yuv_out.hip); every other
+    format takes the exact coefficients of csrc/yuv_fmt.hip."""
+    bit_depth: int = 8
+    matrix: str = "bt601"
+    full_range: bool = False
+
+    def __post_init__(self):
+        if self.bit_depth not in _DEPTHS or isinstance(self.bit_depth, bool):
+            raise ValueError(f"bit_depth is one of {_DEPTHS}, not {self.bit_depth!r}")
+        if self.matrix not in _MATRICES:
+            raise ValueError(f"matrix is one of {_MATRICES}, not {self.matrix!r}")
+        object.__setattr__(self, "bit_depth", int(self.bit_depth))
+        object.__setattr__(self, "full_range", bool(self.full_range))
+
+    @property
+    def peak(self) -> int:
+        return (1 << self.bit_depth) - 1
+
+    @property
+    def sample_bytes(self) -> int:
+        return 1 if self.bit_depth == 8 else 2
+
+    def frame_bytes(self, height: int, width: int) -> int:
+        return height * width * 3 // 2 * self.sample_bytes
+
+    @property
+    def is_legacy(self) -> bool:
+        return self.bit_depth == 8 and self.matrix == "bt601" and not self.full_range
+
+    @property
+    def flags(self) -> int:
+        """The container's code (codec.py): bits 0-1 depth, bit 4 matrix, bit 6 range."""
+        return (_DEPTHS.index(self.bit_depth) | (_FLAG_MATRIX if self.matrix == "bt709" else 0) |
+                (_FLAG_FULL if self.full_range else 0))
+
+    @classmethod
+    def from_flags(cls, flags: int) -> "YuvFormat":
+        flags = int(flags)
+        if flags & ~(_FLAG_DEPTH | _FLAG_MATRIX | _FLAG_FULL):
+            raise ValueError(f"unknown file flags 0x{flags:x}")
+        return cls(_DEPTHS[flags & _FLAG_DEPTH], _MATRICES[1 if flags & _FLAG_MATRIX else 0],
+                   bool(flags & _FLAG_FULL))
+
+    def table(self):
+        """gsvc_yuv_format_table's 18 integers (include/gsvc_amd.h): P, Yoff, Coff,
+        bytes per sample, cY cRV cGU cGV cBU, yR yG yB, uR uG uB, vR vG vB."""
+        b, P = self.bit_depth, float(self.peak)
+        kr, kb = _KR_KB[self.matrix]
+        kg = 1.0 - kr - kb
+        yspan = P if self.full_range else float(219 << (b - 8))
+        cspan = P if self.full_range else float(224 << (b - 8))
+        fix = lambda x: int(math.floor(x * 1048576.0 + 0.5))  # noqa: E731
+        half = fix(cspan / (2.0 * P))
+        return (self.peak, 0 if self.full_range else 16 << (b - 8), 1 << (b - 1), self.sample_bytes,
+                fix(P / yspan), fix(2.0 * (1.0 - kr) * P / cspan), fix(-2.0 * kb * (1.0 - kb) / kg * P / cspan),
+                fix(-2.0 * kr * (1.0 - kr) / kg * P / cspan), fix(2.0 * (1.0 - kb) * P / cspan),
+                fix(kr * yspan / P), fix(kg * yspan / P), fix(kb * yspan / P),
+                fix(-kr / (2.0 * (1.0 - kb)) * cspan / P), fix(-kg / (2.0 * (1.0 - kb)) * cspan / P), half,
+                half, fix(-kg / (2.0 * (1.0 - kr)) * cspan / P), fix(-kb / (2.0 * (1.0 - kr)) * cspan / P))
+
+    def _c(self):
+        """The format as include/gsvc_amd.h's gsvc_yuv_format (three ints)."""
+        return (ctypes.c_int * 3)(self.bit_depth, _MATRICES.index(self.matrix), int(self.full_range))
+
+    def __str__(self):
+        return f"{self.bit_depth}-bit {self.matrix} {'full' if self.full_range else 'limited'} range"
+
+
+def add_format_arguments(parser) -> None:
+    """--bit_depth, --matrix, --full_range of this module's and the codec's command lines."""
+    parser.add_argument("--bit_depth", type=int, choices=_DEPTHS, default=None,
+                        help="bits per sample of the .yuv (default 8; above 8: 16-bit little-endian)")
+    parser.add_argument("--matrix", choices=_MATRICES, default=None, help="default bt601")
+    parser.add_argument("--full_range", action="store_true", default=None, help="full-range YUV (default limited)")
+
+
+def format_of_arguments(args, base: Optional[YuvFormat] = None) -> Optional[YuvFormat]:
+    """The format the three options name, on top of ``base`` (None: the legacy
+    format); None when no option was given and there is no base."""
+    given = (args.bit_depth, args.matrix, args.full_range)
+    if all(g is None for g in given) and base is None:
+        return None
+    base = base or YuvFormat()
+    return YuvFormat(base.bit_depth if given[0] is None else given[0],
+                     base.matrix if given[1] is None else given[1],
+                     base.full_range if given[2] is None else given[2])
+
+
+def _sample_bytes_of(t: torch.Tensor, fmt: YuvFormat, count: int, what: str) -> torch.Tensor:
+    """``t`` (uint8 bytes, or int16 samples of a 16-bit format) as a flat uint8
+    tensor of ``count`` bytes."""
+    if t.dtype == torch.int16 and fmt.sample_bytes == 2:
+        t = t.contiguous().view(torch.uint8)
+    if t.dtype != torch.uint8:
+        raise RuntimeError(f"{what} must be a uint8 tensor (or int16 samples of a 16-bit format)")
+    if t.numel() != count:
+        raise ValueError(f"{what} must hold {count} bytes ({fmt}), not {t.numel()}")
+    return t.reshape(-1)
+
+
+def _samples_int64(raw: torch.Tensor, fmt: YuvFormat) -> torch.Tensor:
+    """Flat uint8 CPU bytes -> int64 samples (little-endian words above 8 bits)."""
+    flat = raw.reshape(-1).to(torch.int64)
+    return flat if fmt.sample_bytes == 1 else flat[0::2] | (flat[1::2] << 8)
+
+
+def _samples_bytes(x: torch.Tensor, fmt: YuvFormat) -> torch.Tensor:
+    """int64 samples [F, n] in [0, P] -> uint8 [F, n * sample_bytes], little-endian."""
+    if fmt.sample_bytes == 1:
+        return x.to(torch.uint8)
+    return torch.stack([x & 255, x >> 8], dim=-1).to(torch.uint8).reshape(x.shape[0], -1)
+
+
+def _yuv420_to_rgb_torch(raw: torch.Tensor, h: int, w: int, fmt: YuvFormat) -> torch.Tensor:
+    """csrc/yuv_fmt.hip's input arithmetic in torch int64 ops (CPU tensors)."""
+    P, yoff, coff, _, cy, crv, cgu, cgv, cbu = fmt.table()[:9]
+    s = _samples_int64(raw, fmt)
+    n, cn = h * w, (h // 2) * (w // 2)
+    y = (s[:n].view(h, w) - yoff).clamp_min(0) * cy + (1 << 19)
+    u, v = ((s[n + k * cn:n + (k + 1) * cn].view(h // 2, w // 2) - coff)
+            .repeat_interleave(2, 0).repeat_interleave(2, 1) for k in (0, 1))
+    rgb = torch.stack([y + crv * v, y + cgv * v + cgu * u, y + cbu * u]) >> 20
+    return (rgb.clamp(0, P).to(torch.float32) / torch.tensor(float(P), dtype=torch.float32))[None].contiguous()
+
+
+def i420_to_rgb(yuv: torch.Tensor, height: int, width: int, fmt: Optional[YuvFormat] = None) -> torch.Tensor:
+    """One planar 4:2:0 frame (its raw bytes: a uint8 tensor of
+    ``fmt.frame_bytes(H, W)``; for a 16-bit format also an int16 tensor of
+    H*W*3/2 samples) -> [1, 3, H, W] float RGB in [0, 1] on the tensor's device.
+    ``fmt`` None or ``YuvFormat()``: 8-bit I420 with OpenCV's BT.601 arithmetic
+    (cv2.cvtColor(COLOR_YUV2RGB_I420) + ToTensor, ``gsvc_i420_to_rgb``); any
+    other format: ``gsvc_yuv420_to_rgb`` (csrc/yuv_fmt.hip).  A CPU tensor takes
+    the same arithmetic in torch integer ops (the codec's encoder on a host
+    without a GPU)."""
     from . import _lib as L
+    if fmt is not None and not fmt.is_legacy:
+        if height <= 0 or width <= 0 or height % 2 or width % 2:
+            raise ValueError("i420_to_rgb: height and width positive and even")
+        raw = _sample_bytes_of(yuv, fmt, fmt.frame_bytes(height, width), "yuv")
+        if not raw.is_cuda:
+            return _yuv420_to_rgb_torch(raw, int(height), int(width), fmt)
+        if not raw.is_contiguous() or raw.data_ptr() % fmt.sample_bytes:
+            raw = raw.clone()  # a 16-bit view at an odd address
+        out = torch.empty((1, 3, height, width), dtype=torch.float32, device=raw.device)
+        L.call("gsvc_yuv420_to_rgb", 1, L.ptr(raw), int(height), int(width), fmt._c(), L.ptr(out),
+               L.stream(raw.device))
+        return out
     if yuv.dtype != torch.uint8:
         raise RuntimeError("yuv must be a uint8 tensor")
     if yuv.numel() != height * width * 3 // 2:
@@ -101,15 +258,67 @@ def _rgb_to_i420_torch(images: torch.Tensor, ref: Optional[torch.Tensor]):
     return out, sse
 
 
-def rgb_to_i420(images: torch.Tensor, ref: Optional[torch.Tensor] = None):
-    """Float RGB images [F, 3, H, W] (or [3, H, W]; any values) -> planar 8-bit
-    I420 frames, uint8 [F, H*W*3/2]: per frame Y, then U and V of half size
-    each way (``gsvc_rgb_to_i420``, csrc/yuv_out.hip: BT.601 limited range,
-    chroma from the 2x2 block's sum; the inverse of ``i420_to_rgb``).  With
-    ``ref`` (source I420 frames, uint8, the output's shape) also returns the
-    exact sums of squared byte differences, int64 [F, 3] (Y, U, V).  CUDA
-    tensors take the kernel, CPU tensors the same arithmetic in torch integer
-    ops; the bytes are the same."""
+def _rgb_to_yuv420_torch(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: YuvFormat):
+    """csrc/yuv_fmt.hip's output arithmetic in torch int64 ops (CPU tensors)."""
+    F_, _, H, W = images.shape
+    P, yoff, coff = fmt.table()[:3]
+    yr, yg, yb, ur, ug, ub, vr, vg, vb = fmt.table()[9:]
+    c = torch.where(images > 0, images, torch.zeros_like(images))  # NaN, -0 -> 0
+    c = torch.where(c < 1, c, torch.ones_like(c))
+    q = (c * float(P) + 0.5).to(torch.int64)  # fp32: one rounding per op, then truncation
+    R, G, B = q[:, 0], q[:, 1], q[:, 2]
+    Y = (yr * R + yg * G + yb * B + ((yoff << 20) + (1 << 19))) >> 20
+    Rs, Gs, Bs = (t.view(F_, H // 2, 2, W // 2, 2).sum(dim=(2, 4)) for t in (R, G, B))
+    U = (ur * Rs + ug * Gs + ub * Bs + ((coff << 22) + (1 << 21))) >> 22
+    V = (vr * Rs + vg * Gs + vb * Bs + ((coff << 22) + (1 << 21))) >> 22
+    planes = torch.cat([t.clamp(0, P).reshape(F_, -1) for t in (Y, U, V)], dim=1)
+    out = _samples_bytes(planes, fmt)
+    if ref is None:
+        return out
+    d = planes - _samples_int64(ref, fmt).view(F_, -1)
+    d = d * d
+    n, cn = H * W, H * W // 4
+    sse = torch.stack([d[:, :n].sum(1), d[:, n:n + cn].sum(1), d[:, n + cn:].sum(1)], dim=1)
+    return out, sse
+
+
+def _rgb_to_yuv420(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: YuvFormat):
+    """``rgb_to_i420`` for a format other than the legacy one."""
+    F_, _, H, W = (int(s) for s in images.shape)
+    size = fmt.frame_bytes(H, W)
+    if ref is not None:
+        if ref.device != images.device:
+            raise ValueError("ref must be on the images' device")
+        ref = _sample_bytes_of(ref, fmt, F_ * size, "ref")
+    if not images.is_cuda:
+        return _rgb_to_yuv420_torch(images.detach().float(), ref, fmt)
+    from . import _lib as L
+    src = images.detach()
+    if src.dtype is not torch.float32 or not src.is_contiguous():
+        src = src.float().contiguous()
+    out = torch.empty((F_, size), dtype=torch.uint8, device=src.device)
+    sse = None
+    if ref is not None:
+        if not ref.is_contiguous() or ref.data_ptr() % fmt.sample_bytes:
+            ref = ref.clone()  # a 16-bit view at an odd address
+        sse = torch.empty((F_, 3), dtype=torch.int64, device=src.device)
+    L.call("gsvc_rgb_to_yuv420", F_, L.ptr(src), H, W, fmt._c(), L.ptr(out), L.ptr(ref), L.ptr(sse),
+           L.stream(src.device))
+    return out if ref is None else (out, sse)
+
+
+def rgb_to_i420(images: torch.Tensor, ref: Optional[torch.Tensor] = None, fmt: Optional[YuvFormat] = None):
+    """Float RGB images [F, 3, H, W] (or [3, H, W]; any values) -> planar 4:2:0
+    frames as the bytes of a .yuv file, uint8 [F, fmt.frame_bytes(H, W)]: per
+    frame Y, then U and V of half size each way, chroma from the 2x2 block's
+    sum; the inverse of ``i420_to_rgb``.  ``fmt`` None or ``YuvFormat()``: 8-bit
+    I420, BT.601 limited range (``gsvc_rgb_to_i420``, csrc/yuv_out.hip); any
+    other format: ``gsvc_rgb_to_yuv420`` (csrc/yuv_fmt.hip; samples above 8 bits
+    as 16-bit little-endian).  With ``ref`` (source frames, uint8, the output's
+    shape; int16 samples for a 16-bit format) also returns the exact sums of
+    squared sample differences, int64 [F, 3] (Y, U, V).  CUDA tensors take the
+    kernel, CPU tensors the same arithmetic in torch integer ops; the bytes
+    are the same."""
     if images.dim() == 3:
         images = images[None]
     if images.dim() != 4 or images.shape[1] != 3 or not images.is_floating_point():
@@ -117,6 +326,8 @@ def rgb_to_i420(images: torch.Tensor, ref: Optional[torch.Tensor] = None):
     F_, _, H, W = (int(s) for s in images.shape)
     if F_ <= 0 or H <= 0 or W <= 0 or H % 2 or W % 2:
         raise ValueError("rgb_to_i420: at least one frame; height and width positive and even")
+    if fmt is not None and not fmt.is_legacy:
+        return _rgb_to_yuv420(images, ref, fmt)
     size = H * W * 3 // 2
     if ref is not None:
         if ref.dtype != torch.uint8 or ref.numel() != F_ * size or ref.device != images.device:
@@ -139,10 +350,12 @@ def rgb_to_i420(images: torch.Tensor, ref: Optional[torch.Tensor] = None):
     return out if ref is None else (out, sse)
 
 
-def load_yuv_frames(path: str, width: int, height: int, device, frames: Optional[Sequence[int]] = None):
+def load_yuv_frames(path: str, width: int, height: int, device, frames: Optional[Sequence[int]] = None,
+                    fmt: Optional[YuvFormat] = None):
     """process_yuv_video (utils.py:134-156) for the 0-based frame indices
-    ``frames`` (all when None): a memory map, one frame at a time to the GPU."""
-    size = width * height * 3 // 2
+    ``frames`` (all when None): a memory map, one frame at a time to the GPU.
+    ``fmt``: the file's pixel format (None: 8-bit I420, BT.601 limited range)."""
+    size = (fmt or YuvFormat()).frame_bytes(height, width)
     total = os.path.getsize(path) // size
     mm = np.memmap(path, dtype=np.uint8, mode="r")
     idx = range(total) if frames is None else frames
@@ -151,7 +364,7 @@ def load_yuv_frames(path: str, width: int, height: int, device, frames: Optional
         if not 0 <= i < total:
             continue
         raw = torch.from_numpy(np.array(mm[i * size:(i + 1) * size])).to(device)
-        out[i] = i420_to_rgb(raw, height, width)
+        out[i] = i420_to_rgb(raw, height, width, fmt)
     return out, total
 
 
@@ -485,7 +698,8 @@ def train_video(frame_fn, num_frames: int, k_frames: Sequence[int], args, rank: 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="GSVC video representation on MI355X")
-    ap.add_argument("-d", "--dataset", type=str, default=None, help="I420 .yuv file")
+    ap.add_argument("-d", "--dataset", type=str, default=None, help="planar 4:2:0 .yuv file")
+    add_format_arguments(ap)  # of --dataset
     ap.add_argument("--synthetic", type=int, default=0, help="frames of a synthetic video")
     ap.add_argument("--cut_every", type=int, default=0, help="synthetic scene-cut period")
     ap.add_argument("--synthetic_kind", choices=["smooth", "textured"], default="smooth",
@@ -550,14 +764,15 @@ def main(argv=None):
         np.random.seed(int(args.seed))
 
     if args.dataset:
-        size = args.width * args.height * 3 // 2
+        fmt = format_of_arguments(args)
+        size = (fmt or YuvFormat()).frame_bytes(args.height, args.width)
         total = os.path.getsize(args.dataset) // size
         num_frames = min(args.image_length, total)
 
         def frame_fn(i, _cache={}):
             if i not in _cache:
                 _cache.clear()
-                fr, _ = load_yuv_frames(args.dataset, args.width, args.height, device, [i])
+                fr, _ = load_yuv_frames(args.dataset, args.width, args.height, device, [i], fmt=fmt)
                 _cache.update(fr)
             return _cache[i]
     else:

@@ -56,7 +56,8 @@ enum gsvc_status {
  * ABI version 3: gsvc_encode_stream_bytes / gsvc_encode_stream added.
  * ABI version 4: gsvc_quant_train_workspace_bytes / gsvc_quant_train_step /
  * gsvc_quant_adan_step added.  gsvc_rgb_to_i420 and gsvc_quant_train_run joined
- * version 4 later: added entries, nothing existing changed. */
+ * version 4 later, and after them gsvc_yuv_format_table, gsvc_yuv420_to_rgb and
+ * gsvc_rgb_to_yuv420: added entries, nothing existing changed. */
 #define GSVC_ABI_VERSION 4
 
 /* Library identity and error reporting. */
@@ -658,6 +659,58 @@ int gsvc_i420_to_rgb(const unsigned char *yuv, int height, int width, float *out
  * the bytewise one; both write the same bytes. */
 int gsvc_rgb_to_i420(int frames, const float *rgb, int height, int width, unsigned char *out,
                      const unsigned char *ref, unsigned long long *sse, void *stream);
+
+/* Pixel formats beyond the two entries above (csrc/yuv_fmt.hip):
+ * planar YUV 4:2:0 of 8, 10, 12 or 16 bits per sample, BT.601 or BT.709, limited
+ * or full range.  Samples of more than 8 bits are 16-bit little-endian words with
+ * the value in the low bits (yuv420p10le, ...12le, ...16le); planes Y, U, V.
+ *
+ * The legacy format {8, 0, 0} belongs to gsvc_i420_to_rgb / gsvc_rgb_to_i420,
+ * which hold OpenCV's three-decimal constants; the two conversion entries below
+ * use exact coefficients, differ from them by a level here and there, and so
+ * REFUSE that one format (GSVC_ERR_ARG): one definition per format.
+ *
+ * With b the depth, s = b - 8, P = 2^b - 1; (Kr, Kb) = (0.299, 0.114) for BT.601,
+ * (0.2126, 0.0722) for BT.709, Kg = 1 - Kr - Kb; limited range Yoff = 16 << s,
+ * Yspan = 219 << s, Cspan = 224 << s, full range Yoff = 0, Yspan = Cspan = P;
+ * Coff = 2^(b-1); fix(x) = floor(x * 2^20 + 0.5) in double:
+ *   cY = fix(P/Yspan), cRV = fix(2(1-Kr) P/Cspan), cGU = fix(-2Kb(1-Kb)/Kg P/Cspan),
+ *   cGV = fix(-2Kr(1-Kr)/Kg P/Cspan), cBU = fix(2(1-Kb) P/Cspan);
+ *   yR = fix(Kr Yspan/P), yG = fix(Kg Yspan/P), yB = fix(Kb Yspan/P);
+ *   uR = fix(-Kr/(2(1-Kb)) Cspan/P), uG = fix(-Kg/(2(1-Kb)) Cspan/P), uB = fix(Cspan/(2P));
+ *   vR = fix(Cspan/(2P)), vG = fix(-Kg/(2(1-Kr)) Cspan/P), vB = fix(-Kb/(2(1-Kr)) Cspan/P). */
+typedef struct {
+    int bit_depth;  /* 8, 10, 12, 16 */
+    int matrix;     /* 0 bt601, 1 bt709 */
+    int full_range; /* 0 limited, 1 full */
+} gsvc_yuv_format;
+
+/* Host only, any of the 16 formats (the legacy one too: a query, not a
+ * conversion): out = P, Yoff, Coff, bytes per sample, then the 14 coefficients
+ * in the order above. */
+int gsvc_yuv_format_table(const gsvc_yuv_format *fmt, long long out[18]);
+
+/* yuv: frames * (H*W*3/2) samples (device) -> out [frames][3][H][W] fp32.  Per
+ * pixel, with the chroma sample of its 2x2 block: y = max(0, Y - Yoff) cY + 2^19,
+ * u = U - Coff, v = V - Coff; R = clamp((y + cRV v) >> 20, 0, P), G = clamp((y +
+ * cGV v + cGU u) >> 20, 0, P), B = clamp((y + cBU u) >> 20, 0, P) (arithmetic
+ * shift; 64-bit above 8 bits); out = (float)X / (float)P.  A 16-bit sample above
+ * P is taken as it is.  H, W even, > 0; a 16-bit buffer at an odd address is an
+ * argument error. */
+int gsvc_yuv420_to_rgb(int frames, const void *yuv, int height, int width,
+                       const gsvc_yuv_format *fmt, float *out, void *stream);
+
+/* The inverse, as gsvc_rgb_to_i420: q = (int)(min(max(x, 0), 1) * (float)P + 0.5f)
+ * (NaN -> 0); Y = clamp((yR R + yG G + yB B + (Yoff << 20) + 2^19) >> 20, 0, P);
+ * with Rs, Gs, Bs the sums of q over a 2x2 block, U = clamp((uR Rs + uG Gs + uB Bs
+ * + (Coff << 22) + 2^21) >> 22, 0, P), V likewise.  out: frames * (H*W*3/2)
+ * samples.  ref: NULL, or source frames in out's layout; then sse[frames][3]
+ * receives the exact sums of squared sample differences (zeroed on the stream by
+ * the entry).  W % 8 == 0 with rgb, out and ref 16-byte aligned takes one lane per
+ * 2 rows x 8 columns, everything else one lane per 2x2 block; same bytes. */
+int gsvc_rgb_to_yuv420(int frames, const float *rgb, int height, int width,
+                       const gsvc_yuv_format *fmt, void *out, const void *ref,
+                       unsigned long long *sse, void *stream);
 
 /* ---- SSIM / MS-SSIM (the loss_fn SSIM variants, utils.py:29-40, and the
  * per-frame MS-SSIM metric, train_video_Represent.py:145), restating

@@ -1,6 +1,7 @@
 """What the I420 output costs a decoder, on one MI355X in one session.
 
     python tools/decodebench.py [--out DIR] [--splats 10000 50000] [--reps 5]
+    python tools/decodebench.py --format 10:bt709:limited [--out DIR] [--splats 10000]
 
 The workload is bench.py's ``video_decode`` (a GOP of 8 distinct 1920x1080
 frame models, seed 4242) at 10k and again at 50k splats per frame.  Measured
@@ -23,7 +24,15 @@ Every figure is the median of ``--reps`` windows between device events (4: a
 host clock around work that ends in a synchronise), each window long enough
 (--window seconds) to be past the clock's and the scheduler's grain, after a
 warm-up of every shape; the variants of one comparison alternate window by
-window, so drift in the shared host hits both.  Fails without a HIP device."""
+window, so drift in the shared host hits both.  Fails without a HIP device.
+
+With ``--format DEPTH:MATRIX:RANGE`` the session measures that
+pixel format's kernels (csrc/yuv_fmt.hip) against the legacy 8-bit ones instead,
+variant against variant in alternating windows: the output conversion alone
+(without and with a reference) and behind ``render_frames_sum``, and the input
+conversion per frame.  The yardstick is the legacy kernel's achieved bytes per
+second in the same session, each kernel over its own algorithmic bytes per
+pixel (12 + 1.5 samples' bytes, + 1.5 samples' with a reference)."""
 import argparse
 import json
 import os
@@ -40,7 +49,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gsvc_amd import codec  # noqa: E402
 from gsvc_amd import compress as C  # noqa: E402
 from gsvc_amd.render import render_frames_sum  # noqa: E402
-from gsvc_amd.video import rgb_to_i420  # noqa: E402
+from gsvc_amd.video import YuvFormat, rgb_to_i420  # noqa: E402
 
 H, W = 1080, 1920
 PEAK_SPEC, PEAK_COPY = 8.0e12, 6.29e12
@@ -120,6 +129,81 @@ def kernel_block(device, frames, splats, reps, seconds):
                           us_per_frame=round(conv[name]["median_us"] / frames, 3))
     res.update(conv)
     return res
+
+
+def format_block(device, fmt, frames, splats, reps, seconds):
+    """The kernels of ``fmt`` against the legacy ones, in one session."""
+    from gsvc_amd import _lib as L
+    xyz, chol, feat = gop_inputs(device, frames, splats)
+    bound = torch.tensor([0.5, 0.0, 0.5], device=device)
+    bg = torch.ones(3, device=device)
+    sizes = [splats] * frames
+    sb = fmt.sample_bytes
+
+    def render():
+        return render_frames_sum(xyz, chol, feat, sizes, H, W, bg, cholesky_bound=bound)
+
+    res = {"format": str(fmt), "frames": frames, "splats": splats}
+    behind = compare({"render_legacy": lambda: rgb_to_i420(render()),
+                      "render_format": lambda: rgb_to_i420(render(), fmt=fmt)}, reps, seconds)
+    behind["ratio"] = round(behind["render_format"]["median_us"] / behind["render_legacy"]["median_us"], 4)
+    res["behind_render"] = behind
+
+    # alone: three batches of images (600 MB: past the Infinity Cache) and their references
+    base = render()
+    batches = [base, (base * 0.5).contiguous(), (1.0 - base).contiguous()]
+    refs = {None: [rgb_to_i420(b.flip(0)) for b in batches], fmt: [rgb_to_i420(b.flip(0), fmt=fmt) for b in batches]}
+    turn = [0]
+
+    def convert(f, with_ref):
+        def run():
+            turn[0] = (turn[0] + 1) % 3
+            return rgb_to_i420(batches[turn[0]], refs[f][turn[0]] if with_ref else None, fmt=f)
+        return run
+
+    def rates(got, pairs):
+        for name, per_pixel, count in pairs:
+            nbytes = count * H * W * per_pixel
+            rate = nbytes / (got[name]["median_us"] * 1e-6)
+            got[name].update(algorithmic_bytes=int(nbytes), tb_per_s=round(rate / 1e12, 3),
+                             share_of_copy_rate=round(rate / PEAK_COPY, 3),
+                             us_per_frame=round(got[name]["median_us"] / count, 3))
+
+    out = compare({"legacy": convert(None, False), "format": convert(fmt, False)}, reps, seconds)
+    rates(out, (("legacy", 13.5, frames), ("format", 12 + 1.5 * sb, frames)))
+    out["rate_ratio"] = round(out["format"]["tb_per_s"] / out["legacy"]["tb_per_s"], 4)
+    res["output"] = out
+    out = compare({"legacy": convert(None, True), "format": convert(fmt, True)}, reps, seconds)
+    rates(out, (("legacy", 15.0, frames), ("format", 12 + 3.0 * sb, frames)))
+    out["rate_ratio"] = round(out["format"]["tb_per_s"] / out["legacy"]["tb_per_s"], 4)
+    res["output_ref"] = out
+
+    # input, one frame per call as load_yuv_frames does; 16 output slots (400 MB) in rotation
+    slots = [torch.empty((1, 3, H, W), dtype=torch.float32, device=device) for _ in range(16)]
+    raw8 = refs[None][0]
+    rawf = refs[fmt][0]
+    c_fmt, stream = fmt._c(), L.stream(device)
+
+    def legacy_in():
+        turn[0] = (turn[0] + 1) % 16
+        L.call("gsvc_i420_to_rgb", L.ptr(raw8[turn[0] % frames]), H, W, L.ptr(slots[turn[0]]), stream)
+
+    def format_in():
+        turn[0] = (turn[0] + 1) % 16
+        L.call("gsvc_yuv420_to_rgb", 1, L.ptr(rawf[turn[0] % frames]), H, W, c_fmt, L.ptr(slots[turn[0]]), stream)
+
+    out = compare({"legacy": legacy_in, "format": format_in}, reps, seconds)
+    rates(out, (("legacy", 13.5, 1), ("format", 12 + 1.5 * sb, 1)))
+    out["rate_ratio"] = round(out["format"]["tb_per_s"] / out["legacy"]["tb_per_s"], 4)
+    res["input"] = out
+    return res
+
+
+def _parse_format(text):
+    depth, matrix, rng = text.split(":")
+    if rng not in ("limited", "full"):
+        raise SystemExit("--format is DEPTH:MATRIX:limited|full, e.g. 10:bt709:limited")
+    return YuvFormat(int(depth), matrix, rng == "full")
 
 
 def _host_i420(rgb):
@@ -207,6 +291,8 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.2, help="seconds per timed window")
+    ap.add_argument("--format", default=None, metavar="DEPTH:MATRIX:RANGE",
+                    help="measure this pixel format's kernels against the legacy ones instead, e.g. 10:bt709:limited")
     ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None,
                     help="where the end-to-end files go (tmpfs)")
     args = ap.parse_args(argv)
@@ -215,6 +301,15 @@ def main(argv=None):
     device = torch.device("cuda:0")
     line = {"device": torch.cuda.get_device_name(0), "H": H, "W": W, "reps": args.reps,
             "window_s": args.window, "kernels": [], "end_to_end": []}
+    if args.format:
+        fmt = _parse_format(args.format)
+        del line["kernels"], line["end_to_end"]
+        line["formats"] = []
+        with torch.no_grad():
+            for splats in args.splats:
+                line["formats"].append(format_block(device, fmt, args.frames, splats, args.reps, args.window))
+                print(json.dumps(line["formats"][-1]), flush=True)
+        return _write(line, args.out)
     with torch.no_grad():
         for splats in args.splats:
             line["kernels"].append(kernel_block(device, args.frames, splats, args.reps, args.window))
@@ -223,9 +318,13 @@ def main(argv=None):
             for splats in args.splats:
                 line["end_to_end"].append(end_to_end(device, splats, args.reps, tmp))
                 print(json.dumps(line["end_to_end"][-1]), flush=True)
-    if args.out:
-        os.makedirs(args.out, exist_ok=True)
-        with open(os.path.join(args.out, "decodebench.json"), "w") as fh:
+    return _write(line, args.out)
+
+
+def _write(line, out):
+    if out:
+        os.makedirs(out, exist_ok=True)
+        with open(os.path.join(out, "decodebench.json"), "w") as fh:
             json.dump(line, fh, indent=1)
             fh.write("\n")
     return line
