@@ -102,6 +102,8 @@ _SIGS = {
     "gsvc_yuv_format_table": [_P, _P],
     "gsvc_yuv420_to_rgb": [_I, _P, _I, _I, _P, _P, _P],
     "gsvc_rgb_to_yuv420": [_I, _P, _I, _I, _P, _P, _P, _P, _P],
+    "gsvc_yuv_to_rgb": [_I, _P, _I, _I, _P, _I, _I, _P, _P],
+    "gsvc_rgb_to_yuv": [_I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P],
     "gsvc_ssim_workspace_bytes": [_I, _I, _I, _I, _I],
     "gsvc_ssim_forward": [_I, _I, _I, _I, _P, _P, _I, _F, _F, _F, _I, _P, _I, _P, _P, _SZ, _P],
     "gsvc_ssim_backward_scratch_bytes": [_I, _I, _I, _I, _I],

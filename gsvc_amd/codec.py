@@ -2,11 +2,12 @@
 
 ``compress.encode_frame`` gives one byte string per frame; this module puts a
 video's frame streams into ONE file with an index (``write_video`` /
-``read_video``), decodes such a file -- or a list of streams -- to planar YUV
-4:2:0 (8-bit I420 by default; 8 to 16 bits, BT.601 or BT.709, limited or full
-range: ``video.YuvFormat``) in batches on the GPU (``decode_video``:
-``decode_frames(output="i420")``, csrc/yuv_out.hip and csrc/yuv_fmt.hip), and
-is the command line of the three steps:
+``read_video``), decodes such a file -- or a list of streams -- to raw YUV
+(8-bit I420 by default; 8 to 16 bits, BT.601 or BT.709, limited or full range,
+4:2:0 / 4:2:2 / 4:4:4, planar or semi-planar as NV12 / P010:
+``video.YuvFormat``) in batches on the GPU (``decode_video``:
+``decode_frames(output="i420")``, csrc/yuv_out.hip, csrc/yuv_fmt.hip and
+csrc/yuv_layout.hip), and is the command line of the three steps:
 
     python -m gsvc_amd.codec encode MODELS.pth SRC.yuv OUT.gsvf --width W --height H
     python -m gsvc_amd.codec info OUT.gsvf
@@ -19,12 +20,15 @@ The container, little-endian:
 
     bytes 0-63      "GSVF", u32 version 1, u32 H, u32 W, u32 num_frames,
                     u32 fps_num, u32 fps_den, u32 flags, u64 index_offset,
-                    u64 file_bytes, zero to 64; flags: the source's pixel
-                    format (video.YuvFormat): bits 0-1 depth (0: 8, 1: 10,
+                    u64 file_bytes, u32 layout, zero to 64; flags: the
+                    source's pixel format (video.YuvFormat): bits 0-1 depth (0: 8, 1: 10,
                     2: 12, 3: 16 bits), bit 4 matrix (0 bt601, 1 bt709),
                     bit 6 full range, every other bit 0 (files written
                     before the format existed have flags 0: 8-bit BT.601
-                    limited range)
+                    limited range); layout (byte 48, the first byte that
+                    was reserved): bits 0-1 chroma (0: 4:2:0, 1: 4:2:2,
+                    2: 4:4:4), bit 4 semi-planar (interleaved U, V), every
+                    other bit 0 (files written before read as planar 4:2:0)
     64 ...          the frame streams of encode_frame (version 1 or 2, any
                     mix), back to back
     index_offset... per frame: u64 offset, u32 length, u32 flags (bit 0: delta,
@@ -55,6 +59,7 @@ FILE_VERSION = 1
 FILE_HEADER_BYTES = 64
 INDEX_ENTRY_BYTES = 16
 _FILE_HEADER = struct.Struct("<4sIIIIIIIQQ")  # magic .. file_bytes: 48 bytes, zero to 64
+_LAYOUT_WORD = struct.Struct("<I")  # at byte 48: YuvFormat.layout_code
 _INDEX_ENTRY = struct.Struct("<QII")
 
 
@@ -123,7 +128,8 @@ def write_video(path, streams: Sequence[bytes], fps=(30, 1), fmt: Optional[YuvFo
     the source's pixel format, kept in the header's flags (None: the legacy
     format, flags 0)."""
     vid = _video_of_streams(streams)
-    flags = (fmt or YuvFormat()).flags
+    fmt = fmt or YuvFormat()
+    flags = fmt.flags
     fps_num, fps_den = int(fps[0]), int(fps[1])
     if fps_num <= 0 or fps_den <= 0:
         raise ValueError("fps is (numerator, denominator), both positive")
@@ -137,6 +143,7 @@ def write_video(path, streams: Sequence[bytes], fps=(30, 1), fmt: Optional[YuvFo
     head = _FILE_HEADER.pack(FILE_MAGIC, FILE_VERSION, vid.H, vid.W, vid.num_frames, fps_num, fps_den, flags,
                              index_offset, file_bytes)
     with open(path, "wb") as fh:
+        head += _LAYOUT_WORD.pack(fmt.layout_code)
         fh.write(head + bytes(FILE_HEADER_BYTES - len(head)))
         for i in range(vid.num_frames):
             fh.write(vid.frame(i))
@@ -161,8 +168,9 @@ def read_video(path) -> Video:
         raise ValueError(f"wrong magic {magic!r}, not {FILE_MAGIC!r}")
     if version != FILE_VERSION:
         raise ValueError(f"file version {version}, not {FILE_VERSION}")
-    fmt = YuvFormat.from_flags(flags)  # ValueError("unknown file flags ...") for an undefined bit
-    if any(blob[_FILE_HEADER.size:FILE_HEADER_BYTES]):
+    # ValueError("unknown file flags ...") for an undefined bit, ("unknown layout code ...")
+    fmt = YuvFormat.from_flags(flags, _LAYOUT_WORD.unpack_from(blob, _FILE_HEADER.size)[0])
+    if any(blob[_FILE_HEADER.size + _LAYOUT_WORD.size:FILE_HEADER_BYTES]):
         raise ValueError("unknown file flags or non-zero reserved header bytes")
     if file_bytes != len(blob):
         raise ValueError(f"file_bytes = {file_bytes}, the file has {len(blob)} (truncated or padded)")
@@ -207,8 +215,8 @@ def _psnr(sse: int, count: int, peak: int = 255) -> float:
 
 def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Optional[range] = None,
                  reference=None, fmt: Optional[YuvFormat] = None) -> dict:
-    """Decode a container file (a path) or a list of frame streams to planar
-    YUV 4:2:0, appended frame by frame to ``out_path`` (a raw .yuv; nothing
+    """Decode a container file (a path) or a list of frame streams to YUV
+    (planar 4:2:0 unless the format says otherwise), appended frame by frame to ``out_path`` (a raw .yuv; nothing
     is written when None).  ``fmt``: the output's pixel format; None means the
     file's own (``Video.format``: the source's; 8-bit I420, BT.601 limited
     range for a stream list and for files written before the header carried
@@ -239,9 +247,10 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
     if frames is not None and frames.step != 1 or not 0 <= a < b <= vid.num_frames:
         raise ValueError(f"frames must be a range(a, b) with 0 <= a < b <= {vid.num_frames}")
     H, W = vid.H, vid.W
-    if H % 2 or W % 2:
-        raise ValueError(f"I420 needs an even height and width, not {H}x{W}")
     fmt = fmt or vid.format
+    if fmt.is_planar420 and (H % 2 or W % 2):
+        raise ValueError(f"I420 needs an even height and width, not {H}x{W}")
+    fmt.check_size(H, W)  # 4:2:2: W even; 4:4:4: any size
     size = fmt.frame_bytes(H, W)
     mm = None
     if reference is not None:
@@ -317,7 +326,7 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
     res = {"frames": b - a, "bytes_written": written, "seconds": seconds}
     if mm is not None:
         tot = np.concatenate(sse_rows).astype(np.int64)
-        n, cn = H * W, H * W // 4
+        n, cn = H * W, math.prod(fmt.chroma_shape(H, W))
         res["psnr_y"] = [_psnr(int(r[0]), n, fmt.peak) for r in tot]
         res["psnr_u"] = [_psnr(int(r[1]), cn, fmt.peak) for r in tot]
         res["psnr_v"] = [_psnr(int(r[2]), cn, fmt.peak) for r in tot]
@@ -340,6 +349,7 @@ def _info(args) -> dict:
             "key_frames": vid.key_frames, "file_bytes": vid.file_bytes,
             "format": {"bit_depth": vid.format.bit_depth, "matrix": vid.format.matrix,
                        "full_range": vid.format.full_range},
+            "chroma": vid.format.chroma, "layout": vid.format.layout, "pix_fmt": vid.format.pix_fmt,
             "bpp": round(8.0 * streams / (vid.num_frames * vid.H * vid.W), 6),
             "splats": vid.sizes, "entropy_coded": sum(v == 2 for v in vid.versions)}
 
@@ -395,7 +405,7 @@ def main(argv=None) -> dict:
     p.set_defaults(run=_decode)
     p = sub.add_parser("encode", help="overfit frame models + source .yuv -> container file")
     p.add_argument("models", help="gmodels_state_dict.pth of gsvc_amd.video (frame_<n> from 1)")
-    p.add_argument("src", help="the source video, planar YUV 4:2:0")
+    p.add_argument("src", help="the source video, raw YUV (planar 4:2:0 unless --chroma / --layout / --pix_fmt)")
     p.add_argument("out")
     p.add_argument("--width", type=int, required=True)
     p.add_argument("--height", type=int, required=True)

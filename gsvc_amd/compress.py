@@ -834,11 +834,13 @@ def unpack_frames(streams: Sequence[bytes], device, cholesky_bound=None, prev=No
 def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: bool = False,
                   output: str = "rgb", reference=None, fmt=None):
     """Frame streams (``encode_frame``, either version, in any mix) to images
-    [F, 3, H, W], or with ``output="i420"`` to planar 4:2:0 frames, uint8
-    [F, fmt.frame_bytes(H, W)] (``video.rgb_to_i420`` of those images in the
-    pixel format ``fmt``, a ``video.YuvFormat``; None: 8-bit I420, BT.601
-    limited range; with ``reference``, the source's frames in that format,
-    the pair (frames, int64 [F, 3] squared error)).
+    [F, 3, H, W], or with ``output="i420"`` (or, beside a ``fmt``, its synonym
+    ``"yuv"``) to YUV
+    frames, uint8 [F, fmt.frame_bytes(H, W)] (``video.rgb_to_i420`` of those
+    images in the pixel format ``fmt``, a ``video.YuvFormat`` of any depth,
+    chroma and layout; None: planar 8-bit I420, BT.601 limited range; with
+    ``reference``, the source's frames in that format, the pair (frames, int64
+    [F, 3] squared error)).
 
     On a HIP device: one unpack launch for all frames, then
     ``render_frames_sum``.  A delta frame adds the DECODED parameters of the
@@ -846,8 +848,12 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
     (``return_state=True`` also returns (xq, Lpre, cq) of the last frame).
     CPU: the numpy decoder and the CPU operators, frame by frame."""
     device = torch.device(device)
-    if output not in ("rgb", "i420"):
-        raise ValueError(f"decode_frames: output is 'rgb' or 'i420', not {output!r}")
+    if output not in ("rgb", "i420", "yuv"):
+        raise ValueError(f"decode_frames: output is 'rgb', 'i420' or 'yuv', not {output!r}")
+    if output == "yuv":  # a synonym: the frames of ``fmt``, whatever its chroma and layout
+        if fmt is None:  # without a format it stays the error it was
+            raise ValueError("decode_frames: output='yuv' names the frames of a pixel format: pass fmt=")
+        output = "i420"
     if reference is not None and output != "i420":
         raise ValueError("decode_frames: reference frames are compared in I420 (output='i420')")
     if fmt is not None and output != "i420":

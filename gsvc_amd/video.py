@@ -7,8 +7,9 @@ detect_outliers_mean_diff :214-229) that runs on the MI355X path:
 * frames come from a planar YUV 4:2:0 file (converted on the GPU: 8-bit I420
   by ``gsvc_i420_to_rgb``, OpenCV's BT.601 arithmetic; 10, 12 and 16 bits,
   BT.709 and full range by ``gsvc_yuv420_to_rgb``, ``--bit_depth --matrix
-  --full_range``) or from a seeded synthetic video (the UVG sequences are not
-  in this image);
+  --full_range``; 4:2:2, 4:4:4 and semi-planar NV12 / P010 files by
+  ``gsvc_yuv_to_rgb``, ``--chroma --layout --pix_fmt``) or from a seeded
+  synthetic video (the UVG sequences are not in this image);
 * K-frames (key frames, trained from scratch) come from
   ``<savdir>/<data>/K_frames.txt`` when present, else from the reference's
   detector (500 scratch iterations and a 100-iteration P-probe per frame,
@@ -66,25 +67,50 @@ _KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 _FLAG_DEPTH, _FLAG_MATRIX, _FLAG_FULL = 0x3, 0x10, 0x40
 
 
+_CHROMAS = ("420", "422", "444")   # the layout code's bits 0-1
+_LAYOUTS = ("planar", "semi")      # the layout code's bit 4
+_LAYOUT_CHROMA, _LAYOUT_SEMI = 0x3, 0x10
+# the legacy triple's constants (csrc/yuv.hip, csrc/yuv_out.hip: OpenCV's three
+# decimals) in gsvc_yuv_format_table's order: what the layouts beyond planar
+# 4:2:0 compute with at 8-bit bt601 limited range
+_LEGACY_TABLE = (255, 16, 128, 1, 1220542, 1673527, -409993, -852492, 2116026, 269484, 528482, 102760,
+                 -155188, -305135, 460324, 460324, -385875, -74448)
+
+
 @dataclasses.dataclass(frozen=True)
 class YuvFormat:
-    """A planar YUV 4:2:0 pixel format: ``bit_depth`` 8, 10, 12 or 16 (above 8
-    bits: 16-bit little-endian samples, the value in the low bits, as
-    yuv420p10le), ``matrix`` "bt601" or "bt709", limited or full range.
-    ``YuvFormat()`` is the legacy format (8-bit BT.601 limited range), which
-    keeps OpenCV's arithmetic (csrc/yuv.hip, csrc/yuv_out.hip); every other
-    format takes the exact coefficients of csrc/yuv_fmt.hip."""
+    """A YUV pixel format: ``bit_depth`` 8, 10, 12 or 16, ``matrix`` "bt601" or
+    "bt709", limited or full range, ``chroma`` "420", "422" or "444", ``layout``
+    "planar" (planes Y, U, V) or "semi" (plane Y, then one plane of interleaved
+    U, V pairs, U first: NV12 / NV16 / NV24).  Above 8 bits the samples are
+    16-bit little-endian words: planar with the value in the low bits
+    (yuv420p10le), semi-planar with the value in the high bits (the P010
+    family: word = value << (16 - bit_depth)).
+    ``YuvFormat()`` is the legacy format (planar 4:2:0, 8-bit BT.601 limited
+    range), which keeps OpenCV's arithmetic (csrc/yuv.hip, csrc/yuv_out.hip);
+    every other planar 4:2:0 format takes the exact coefficients of
+    csrc/yuv_fmt.hip, every other chroma or layout
+    csrc/yuv_layout.hip."""
     bit_depth: int = 8
     matrix: str = "bt601"
     full_range: bool = False
+    chroma: str = "420"
+    layout: str = "planar"
 
     def __post_init__(self):
         if self.bit_depth not in _DEPTHS or isinstance(self.bit_depth, bool):
             raise ValueError(f"bit_depth is one of {_DEPTHS}, not {self.bit_depth!r}")
         if self.matrix not in _MATRICES:
             raise ValueError(f"matrix is one of {_MATRICES}, not {self.matrix!r}")
+        chroma = str(self.chroma) if isinstance(self.chroma, int) and not isinstance(self.chroma, bool) \
+            else self.chroma
+        if chroma not in _CHROMAS:
+            raise ValueError(f"chroma is one of {_CHROMAS}, not {self.chroma!r}")
+        if self.layout not in _LAYOUTS:
+            raise ValueError(f"layout is one of {_LAYOUTS}, not {self.layout!r}")
         object.__setattr__(self, "bit_depth", int(self.bit_depth))
         object.__setattr__(self, "full_range", bool(self.full_range))
+        object.__setattr__(self, "chroma", chroma)
 
     @property
     def peak(self) -> int:
@@ -94,12 +120,48 @@ class YuvFormat:
     def sample_bytes(self) -> int:
         return 1 if self.bit_depth == 8 else 2
 
+    @property
+    def is_planar420(self) -> bool:
+        """The layout of the four entries of before (csrc/yuv*.hip but yuv_layout.hip)."""
+        return self.chroma == "420" and self.layout == "planar"
+
+    @property
+    def msb_shift(self) -> int:
+        """Semi-planar words carry the value in the high bits: word = value << msb_shift."""
+        return 16 - self.bit_depth if self.layout == "semi" and self.bit_depth > 8 else 0
+
+    def chroma_shape(self, height: int, width: int):
+        """(rows, columns) of the U samples (and of the V samples) of an H x W frame."""
+        return (height // 2 if self.chroma == "420" else height,
+                width if self.chroma == "444" else width // 2)
+
+    def check_size(self, height: int, width: int) -> None:
+        """ValueError unless H x W fits the chroma: 4:2:0 both even, 4:2:2 W even."""
+        if height <= 0 or width <= 0:
+            raise ValueError(f"height and width must be positive, not {height}x{width}")
+        if self.chroma == "420" and (height % 2 or width % 2):
+            raise ValueError(f"4:2:0 needs an even height and width, not {height}x{width}")
+        if self.chroma == "422" and width % 2:
+            raise ValueError(f"4:2:2 needs an even width, not {height}x{width}")
+
+    def plane_shapes(self, height: int, width: int):
+        """The planes of one frame in file order, as (rows, samples per row):
+        planar Y, U, V; semi-planar Y and the interleaved plane."""
+        self.check_size(height, width)
+        ch, cw = self.chroma_shape(height, width)
+        if self.layout == "semi":
+            return ((height, width), (ch, 2 * cw))
+        return ((height, width), (ch, cw), (ch, cw))
+
     def frame_bytes(self, height: int, width: int) -> int:
-        return height * width * 3 // 2 * self.sample_bytes
+        if self.chroma == "420":
+            return height * width * 3 // 2 * self.sample_bytes
+        ch, cw = self.chroma_shape(height, width)
+        return (height * width + 2 * ch * cw) * self.sample_bytes
 
     @property
     def is_legacy(self) -> bool:
-        return self.bit_depth == 8 and self.matrix == "bt601" and not self.full_range
+        return self.bit_depth == 8 and self.matrix == "bt601" and not self.full_range and self.is_planar420
 
     @property
     def flags(self) -> int:
@@ -107,13 +169,42 @@ class YuvFormat:
         return (_DEPTHS.index(self.bit_depth) | (_FLAG_MATRIX if self.matrix == "bt709" else 0) |
                 (_FLAG_FULL if self.full_range else 0))
 
+    @property
+    def layout_code(self) -> int:
+        """The container's layout word (codec.py): bits 0-1 chroma (0: 420, 1: 422,
+        2: 444), bit 4 semi-planar."""
+        return _CHROMAS.index(self.chroma) | (_LAYOUT_SEMI if self.layout == "semi" else 0)
+
     @classmethod
-    def from_flags(cls, flags: int) -> "YuvFormat":
-        flags = int(flags)
+    def from_flags(cls, flags: int, layout_code: int = 0) -> "YuvFormat":
+        flags, layout_code = int(flags), int(layout_code)
         if flags & ~(_FLAG_DEPTH | _FLAG_MATRIX | _FLAG_FULL):
             raise ValueError(f"unknown file flags 0x{flags:x}")
+        if layout_code & ~(_LAYOUT_CHROMA | _LAYOUT_SEMI) or (layout_code & _LAYOUT_CHROMA) >= len(_CHROMAS):
+            raise ValueError(f"unknown layout code 0x{layout_code & 0xffffffff:x}")
         return cls(_DEPTHS[flags & _FLAG_DEPTH], _MATRICES[1 if flags & _FLAG_MATRIX else 0],
-                   bool(flags & _FLAG_FULL))
+                   bool(flags & _FLAG_FULL), _CHROMAS[layout_code & _LAYOUT_CHROMA],
+                   _LAYOUTS[1 if layout_code & _LAYOUT_SEMI else 0])
+
+    @property
+    def pix_fmt(self) -> str:
+        """ffmpeg's name of the depth, chroma and layout (matrix and range are not
+        part of it): yuv420p, yuv422p10le, nv12, p010le, p210le, ..."""
+        if self.layout == "planar":
+            return f"yuv{self.chroma}p" + ("" if self.bit_depth == 8 else f"{self.bit_depth}le")
+        if self.bit_depth == 8:
+            return {"420": "nv12", "422": "nv16", "444": "nv24"}[self.chroma]
+        return f"p{_CHROMAS.index(self.chroma) * 2}{self.bit_depth}le"
+
+    @classmethod
+    def from_pix_fmt(cls, name: str, matrix: str = "bt601", full_range: bool = False) -> "YuvFormat":
+        for depth in _DEPTHS:
+            for chroma in _CHROMAS:
+                for layout in _LAYOUTS:
+                    fmt = cls(depth, matrix, full_range, chroma, layout)
+                    if fmt.pix_fmt == name:
+                        return fmt
+        raise ValueError(f"unknown pix_fmt {name!r}")
 
     def table(self):
         """gsvc_yuv_format_table's 18 integers (include/gsvc_amd.h): P, Yoff, Coff,
@@ -132,32 +223,59 @@ class YuvFormat:
                 fix(-kr / (2.0 * (1.0 - kb)) * cspan / P), fix(-kg / (2.0 * (1.0 - kb)) * cspan / P), half,
                 half, fix(-kg / (2.0 * (1.0 - kr)) * cspan / P), fix(-kb / (2.0 * (1.0 - kr)) * cspan / P))
 
+    def conversion_table(self):
+        """The 18 integers the conversions compute with: ``table()``, but the
+        legacy kernels' constants for the legacy colour triple (8-bit bt601
+        limited range), in any chroma and layout: one definition per triple."""
+        if self.bit_depth == 8 and self.matrix == "bt601" and not self.full_range:
+            return _LEGACY_TABLE
+        return self.table()
+
     def _c(self):
         """The format as include/gsvc_amd.h's gsvc_yuv_format (three ints)."""
         return (ctypes.c_int * 3)(self.bit_depth, _MATRICES.index(self.matrix), int(self.full_range))
 
     def __str__(self):
-        return f"{self.bit_depth}-bit {self.matrix} {'full' if self.full_range else 'limited'} range"
+        s = f"{self.bit_depth}-bit {self.matrix} {'full' if self.full_range else 'limited'} range"
+        if self.is_planar420:
+            return s
+        return f"{s} {self.chroma[0]}:{self.chroma[1]}:{self.chroma[2]} {self.layout}"
 
 
 def add_format_arguments(parser) -> None:
-    """--bit_depth, --matrix, --full_range of this module's and the codec's command lines."""
+    """--bit_depth, --matrix, --full_range, --chroma, --layout and --pix_fmt of
+    this module's and the codec's command lines."""
     parser.add_argument("--bit_depth", type=int, choices=_DEPTHS, default=None,
                         help="bits per sample of the .yuv (default 8; above 8: 16-bit little-endian)")
     parser.add_argument("--matrix", choices=_MATRICES, default=None, help="default bt601")
     parser.add_argument("--full_range", action="store_true", default=None, help="full-range YUV (default limited)")
+    parser.add_argument("--chroma", choices=_CHROMAS, default=None, help="chroma subsampling (default 420)")
+    parser.add_argument("--layout", choices=_LAYOUTS, default=None,
+                        help="planar (Y, U, V; default) or semi (Y, interleaved UV: NV12 / P010)")
+    parser.add_argument("--pix_fmt", default=None, metavar="NAME",
+                        help="ffmpeg's name for depth, chroma and layout at once: yuv422p10le, nv12, p010le, ...")
 
 
 def format_of_arguments(args, base: Optional[YuvFormat] = None) -> Optional[YuvFormat]:
-    """The format the three options name, on top of ``base`` (None: the legacy
-    format); None when no option was given and there is no base."""
-    given = (args.bit_depth, args.matrix, args.full_range)
+    """The format the options name, on top of ``base`` (None: the legacy
+    format); None when no option was given and there is no base.  --pix_fmt
+    sets depth, chroma and layout; one of those three beside it with another
+    value is a ValueError."""
+    depth, chroma, layout = args.bit_depth, getattr(args, "chroma", None), getattr(args, "layout", None)
+    name = getattr(args, "pix_fmt", None)
+    if name is not None:
+        named = YuvFormat.from_pix_fmt(name)
+        for opt, given, val in (("--bit_depth", depth, named.bit_depth), ("--chroma", chroma, named.chroma),
+                                ("--layout", layout, named.layout)):
+            if given is not None and given != val:
+                raise ValueError(f"--pix_fmt {name} has {opt} {val}, not {given}")
+        depth, chroma, layout = named.bit_depth, named.chroma, named.layout
+    given = (depth, args.matrix, args.full_range, chroma, layout)
     if all(g is None for g in given) and base is None:
         return None
     base = base or YuvFormat()
-    return YuvFormat(base.bit_depth if given[0] is None else given[0],
-                     base.matrix if given[1] is None else given[1],
-                     base.full_range if given[2] is None else given[2])
+    return YuvFormat(*(getattr(base, f) if g is None else g
+                       for f, g in zip(("bit_depth", "matrix", "full_range", "chroma", "layout"), given)))
 
 
 def _sample_bytes_of(t: torch.Tensor, fmt: YuvFormat, count: int, what: str) -> torch.Tensor:
@@ -185,6 +303,108 @@ def _samples_bytes(x: torch.Tensor, fmt: YuvFormat) -> torch.Tensor:
     return torch.stack([x & 255, x >> 8], dim=-1).to(torch.uint8).reshape(x.shape[0], -1)
 
 
+def _split_planes(s: torch.Tensor, h: int, w: int, fmt: YuvFormat):
+    """int64 words [F, samples per frame] of any chroma and layout -> values
+    Y [F, h, w], U, V [F, ch, cw] (the P010 family's low bits dropped)."""
+    s = s >> fmt.msb_shift
+    f, n = s.shape[0], h * w
+    ch, cw = fmt.chroma_shape(h, w)
+    y = s[:, :n].view(f, h, w)
+    if fmt.layout == "semi":
+        uv = s[:, n:].view(f, ch, cw, 2)
+        return y, uv[..., 0], uv[..., 1]
+    return y, s[:, n:n + ch * cw].view(f, ch, cw), s[:, n + ch * cw:].view(f, ch, cw)
+
+
+def _join_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, fmt: YuvFormat) -> torch.Tensor:
+    """The inverse of ``_split_planes``: int64 words [F, samples per frame]."""
+    f = y.shape[0]
+    if fmt.layout == "semi":
+        c = [torch.stack([u, v], dim=-1).reshape(f, -1)]
+    else:
+        c = [u.reshape(f, -1), v.reshape(f, -1)]
+    return torch.cat([y.reshape(f, -1)] + c, dim=1) << fmt.msb_shift
+
+
+def _yuv_to_rgb_torch(raw: torch.Tensor, h: int, w: int, fmt: YuvFormat) -> torch.Tensor:
+    """csrc/yuv_layout.hip's input arithmetic in torch int64 ops (CPU tensors)."""
+    P, yoff, coff, _, cy, crv, cgu, cgv, cbu = fmt.conversion_table()[:9]
+    y, u, v = _split_planes(_samples_int64(raw, fmt)[None], h, w, fmt)
+    y = (y[0] - yoff).clamp_min(0) * cy + (1 << 19)
+    ry, rx = (2 if fmt.chroma == "420" else 1), (1 if fmt.chroma == "444" else 2)
+    u, v = ((t[0] - coff).repeat_interleave(ry, 0).repeat_interleave(rx, 1) for t in (u, v))
+    rgb = torch.stack([y + crv * v, y + cgv * v + cgu * u, y + cbu * u]) >> 20
+    return (rgb.clamp(0, P).to(torch.float32) / torch.tensor(float(P), dtype=torch.float32))[None].contiguous()
+
+
+def _rgb_to_yuv_torch(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: YuvFormat):
+    """csrc/yuv_layout.hip's output arithmetic in torch int64 ops (CPU tensors)."""
+    F_, _, H, W = images.shape
+    P, yoff, coff = fmt.conversion_table()[:3]
+    yr, yg, yb, ur, ug, ub, vr, vg, vb = fmt.conversion_table()[9:]
+    c = torch.where(images > 0, images, torch.zeros_like(images))  # NaN, -0 -> 0
+    c = torch.where(c < 1, c, torch.ones_like(c))
+    q = (c * float(P) + 0.5).to(torch.int64)  # fp32: one rounding per op, then truncation
+    R, G, B = q[:, 0], q[:, 1], q[:, 2]
+    Y = (yr * R + yg * G + yb * B + ((yoff << 20) + (1 << 19))) >> 20
+    ch, cw = fmt.chroma_shape(H, W)
+    Rs, Gs, Bs = (t.view(F_, ch, H // ch, cw, W // cw).sum(dim=(2, 4)) for t in (R, G, B))
+    sh = 20 + (H // ch).bit_length() + (W // cw).bit_length() - 2  # 20 + log2 of the block's pixels
+    U = (ur * Rs + ug * Gs + ub * Bs + ((coff << sh) + (1 << (sh - 1)))) >> sh
+    V = (vr * Rs + vg * Gs + vb * Bs + ((coff << sh) + (1 << (sh - 1)))) >> sh
+    planes = [t.clamp(0, P) for t in (Y, U, V)]
+    out = _samples_bytes(_join_planes(*planes, fmt), fmt)
+    if ref is None:
+        return out
+    rp = _split_planes(_samples_int64(ref, fmt).view(F_, -1), H, W, fmt)
+    sse = torch.stack([((a - b) * (a - b)).reshape(F_, -1).sum(1) for a, b in zip(planes, rp)], dim=1)
+    return out, sse
+
+
+def _yuv_to_rgb(yuv: torch.Tensor, height: int, width: int, fmt: YuvFormat) -> torch.Tensor:
+    """``i420_to_rgb`` for a chroma or layout other than planar 4:2:0."""
+    height, width = int(height), int(width)
+    fmt.check_size(height, width)
+    raw = _sample_bytes_of(yuv, fmt, fmt.frame_bytes(height, width), "yuv")
+    if not raw.is_cuda:
+        return _yuv_to_rgb_torch(raw, height, width, fmt)
+    from . import _lib as L
+    if not raw.is_contiguous() or raw.data_ptr() % fmt.sample_bytes:
+        raw = raw.clone()  # a 16-bit view at an odd address
+    out = torch.empty((1, 3, height, width), dtype=torch.float32, device=raw.device)
+    L.call("gsvc_yuv_to_rgb", 1, L.ptr(raw), height, width, fmt._c(), int(fmt.chroma),
+           int(fmt.layout == "semi"), L.ptr(out), L.stream(raw.device))
+    return out
+
+
+def _rgb_to_yuv(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: YuvFormat):
+    """``rgb_to_i420`` for a chroma or layout other than planar 4:2:0."""
+    F_, _, H, W = (int(s) for s in images.shape)
+    if F_ <= 0:
+        raise ValueError("rgb_to_i420: at least one frame")
+    fmt.check_size(H, W)
+    size = fmt.frame_bytes(H, W)
+    if ref is not None:
+        if ref.device != images.device:
+            raise ValueError("ref must be on the images' device")
+        ref = _sample_bytes_of(ref, fmt, F_ * size, "ref")
+    if not images.is_cuda:
+        return _rgb_to_yuv_torch(images.detach().float(), ref, fmt)
+    from . import _lib as L
+    src = images.detach()
+    if src.dtype is not torch.float32 or not src.is_contiguous():
+        src = src.float().contiguous()
+    out = torch.empty((F_, size), dtype=torch.uint8, device=src.device)
+    sse = None
+    if ref is not None:
+        if not ref.is_contiguous() or ref.data_ptr() % fmt.sample_bytes:
+            ref = ref.clone()  # a 16-bit view at an odd address
+        sse = torch.empty((F_, 3), dtype=torch.int64, device=src.device)
+    L.call("gsvc_rgb_to_yuv", F_, L.ptr(src), H, W, fmt._c(), int(fmt.chroma), int(fmt.layout == "semi"),
+           L.ptr(out), L.ptr(ref), L.ptr(sse), L.stream(src.device))
+    return out if ref is None else (out, sse)
+
+
 def _yuv420_to_rgb_torch(raw: torch.Tensor, h: int, w: int, fmt: YuvFormat) -> torch.Tensor:
     """csrc/yuv_fmt.hip's input arithmetic in torch int64 ops (CPU tensors)."""
     P, yoff, coff, _, cy, crv, cgu, cgv, cbu = fmt.table()[:9]
@@ -203,10 +423,14 @@ def i420_to_rgb(yuv: torch.Tensor, height: int, width: int, fmt: Optional[YuvFor
     H*W*3/2 samples) -> [1, 3, H, W] float RGB in [0, 1] on the tensor's device.
     ``fmt`` None or ``YuvFormat()``: 8-bit I420 with OpenCV's BT.601 arithmetic
     (cv2.cvtColor(COLOR_YUV2RGB_I420) + ToTensor, ``gsvc_i420_to_rgb``); any
-    other format: ``gsvc_yuv420_to_rgb`` (csrc/yuv_fmt.hip).  A CPU tensor takes
-    the same arithmetic in torch integer ops (the codec's encoder on a host
-    without a GPU)."""
+    other planar 4:2:0 format: ``gsvc_yuv420_to_rgb`` (csrc/yuv_fmt.hip); 4:2:2,
+    4:4:4 and semi-planar frames (``fmt.chroma``, ``fmt.layout``; any height at
+    4:2:2, any size at 4:4:4): ``gsvc_yuv_to_rgb`` (csrc/yuv_layout.hip).  A CPU
+    tensor takes the same arithmetic in torch integer ops (the codec's encoder
+    on a host without a GPU)."""
     from . import _lib as L
+    if fmt is not None and not fmt.is_planar420:
+        return _yuv_to_rgb(yuv, height, width, fmt)
     if fmt is not None and not fmt.is_legacy:
         if height <= 0 or width <= 0 or height % 2 or width % 2:
             raise ValueError("i420_to_rgb: height and width positive and even")
@@ -314,7 +538,9 @@ def rgb_to_i420(images: torch.Tensor, ref: Optional[torch.Tensor] = None, fmt: O
     sum; the inverse of ``i420_to_rgb``.  ``fmt`` None or ``YuvFormat()``: 8-bit
     I420, BT.601 limited range (``gsvc_rgb_to_i420``, csrc/yuv_out.hip); any
     other format: ``gsvc_rgb_to_yuv420`` (csrc/yuv_fmt.hip; samples above 8 bits
-    as 16-bit little-endian).  With ``ref`` (source frames, uint8, the output's
+    as 16-bit little-endian); 4:2:2, 4:4:4 and semi-planar output (chroma from
+    the 2x1 block's sum or the pixel itself; U, V interleaved; the P010 family's
+    words): ``gsvc_rgb_to_yuv`` (csrc/yuv_layout.hip).  With ``ref`` (source frames, uint8, the output's
     shape; int16 samples for a 16-bit format) also returns the exact sums of
     squared sample differences, int64 [F, 3] (Y, U, V).  CUDA tensors take the
     kernel, CPU tensors the same arithmetic in torch integer ops; the bytes
@@ -324,6 +550,8 @@ def rgb_to_i420(images: torch.Tensor, ref: Optional[torch.Tensor] = None, fmt: O
     if images.dim() != 4 or images.shape[1] != 3 or not images.is_floating_point():
         raise ValueError("images must be a float tensor [F, 3, H, W] or [3, H, W]")
     F_, _, H, W = (int(s) for s in images.shape)
+    if fmt is not None and not fmt.is_planar420:
+        return _rgb_to_yuv(images, ref, fmt)
     if F_ <= 0 or H <= 0 or W <= 0 or H % 2 or W % 2:
         raise ValueError("rgb_to_i420: at least one frame; height and width positive and even")
     if fmt is not None and not fmt.is_legacy:
@@ -698,7 +926,8 @@ def train_video(frame_fn, num_frames: int, k_frames: Sequence[int], args, rank: 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="GSVC video representation on MI355X")
-    ap.add_argument("-d", "--dataset", type=str, default=None, help="planar 4:2:0 .yuv file")
+    ap.add_argument("-d", "--dataset", type=str, default=None,
+                    help="raw .yuv file (planar 4:2:0 unless --chroma / --layout / --pix_fmt say otherwise)")
     add_format_arguments(ap)  # of --dataset
     ap.add_argument("--synthetic", type=int, default=0, help="frames of a synthetic video")
     ap.add_argument("--cut_every", type=int, default=0, help="synthetic scene-cut period")

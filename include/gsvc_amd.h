@@ -57,7 +57,8 @@ enum gsvc_status {
  * ABI version 4: gsvc_quant_train_workspace_bytes / gsvc_quant_train_step /
  * gsvc_quant_adan_step added.  gsvc_rgb_to_i420 and gsvc_quant_train_run joined
  * version 4 later, and after them gsvc_yuv_format_table, gsvc_yuv420_to_rgb and
- * gsvc_rgb_to_yuv420: added entries, nothing existing changed. */
+ * gsvc_rgb_to_yuv420, then gsvc_yuv_to_rgb and gsvc_rgb_to_yuv: added entries,
+ * nothing existing changed. */
 #define GSVC_ABI_VERSION 4
 
 /* Library identity and error reporting. */
@@ -711,6 +712,45 @@ int gsvc_yuv420_to_rgb(int frames, const void *yuv, int height, int width,
 int gsvc_rgb_to_yuv420(int frames, const float *rgb, int height, int width,
                        const gsvc_yuv_format *fmt, void *out, const void *ref,
                        unsigned long long *sse, void *stream);
+
+/* Chroma layouts beyond planar 4:2:0 (csrc/yuv_layout.hip), for
+ * every gsvc_yuv_format: chroma = 420, 422 or 444; semi_planar = 0: planes Y, U,
+ * V; 1: plane Y, then one plane of interleaved U, V pairs, U first (NV12 / NV16 /
+ * NV24).  Samples per frame: Y H*W; U and V each (H/2)*(W/2) at 420 (H, W even),
+ * H*(W/2) at 422 (W even), H*W at 444 (any H, W > 0).  Above 8 bits a planar word
+ * holds the value in its low bits, a semi-planar word in its high bits (the P010
+ * family: word = value << (16 - b); read as word >> (16 - b), the low bits
+ * ignored; written with the low bits zero).
+ *
+ * The formulas are those of the two entries above with the chroma block
+ * generalised: pixel (i, j) takes the chroma sample at (i >> 1, j >> 1), (i,
+ * j >> 1) or (i, j); on output Rs, Gs, Bs are the sums of q over the sample's
+ * block of n = 4, 2 or 1 pixels and U = clamp((uR Rs + uG Gs + uB Bs + (Coff <<
+ * sh) + 2^(sh-1)) >> sh, 0, P) with sh = 20 + log2 n, V likewise.  Coefficients:
+ * gsvc_yuv_format_table's, except for the legacy triple {8, 0, 0}, which takes
+ * the constants of gsvc_i420_to_rgb / gsvc_rgb_to_i420 (one definition per
+ * colour triple: NV12 out is a byte permutation of gsvc_rgb_to_i420's I420).
+ *
+ * Planar 4:2:0 (chroma 420, semi_planar 0) belongs to the four entries above and
+ * is REFUSED here (GSVC_ERR_ARG).  GSVC_ERR_ARG before any launch also for: a
+ * chroma other than the three, a bad format, frames <= 0, a size that breaks the
+ * chroma's constraint, a missing buffer, ref without sse, a 16-bit buffer at an
+ * odd address.  W % 8 == 0 with every buffer 16-byte aligned takes one lane per
+ * 2 (420) or 1 rows x 8 columns, everything else one lane per chroma block; same
+ * bytes.
+ *
+ * yuv: frames of the layout (device) -> out [frames][3][H][W] fp32. */
+int gsvc_yuv_to_rgb(int frames, const void *yuv, int height, int width, const gsvc_yuv_format *fmt,
+                    int chroma, int semi_planar, float *out, void *stream);
+
+/* rgb [frames][3][H][W] fp32 (any values) -> out: frames of the layout.  ref: NULL,
+ * or source frames in out's layout (U and V taken apart from an interleaved
+ * plane, the P010 family's low bits ignored); then sse[frames][3] (Y, U, V)
+ * receives the exact sums of squared sample differences (zeroed on the stream by
+ * the entry). */
+int gsvc_rgb_to_yuv(int frames, const float *rgb, int height, int width, const gsvc_yuv_format *fmt,
+                    int chroma, int semi_planar, void *out, const void *ref,
+                    unsigned long long *sse, void *stream);
 
 /* ---- SSIM / MS-SSIM (the loss_fn SSIM variants, utils.py:29-40, and the
  * per-frame MS-SSIM metric, train_video_Represent.py:145), restating

@@ -2,6 +2,7 @@
 
     python tools/decodebench.py [--out DIR] [--splats 10000 50000] [--reps 5]
     python tools/decodebench.py --format 10:bt709:limited [--out DIR] [--splats 10000]
+    python tools/decodebench.py --format 10:bt709:limited:422:planar 8:bt601:limited:420:semi ...
 
 The workload is bench.py's ``video_decode`` (a GOP of 8 distinct 1920x1080
 frame models, seed 4242) at 10k and again at 50k splats per frame.  Measured
@@ -32,7 +33,11 @@ variant against variant in alternating windows: the output conversion alone
 (without and with a reference) and behind ``render_frames_sum``, and the input
 conversion per frame.  The yardstick is the legacy kernel's achieved bytes per
 second in the same session, each kernel over its own algorithmic bytes per
-pixel (12 + 1.5 samples' bytes, + 1.5 samples' with a reference)."""
+pixel (12 + 1.5 samples' bytes, + 1.5 samples' with a reference).  With
+``--format DEPTH:MATRIX:RANGE:CHROMA:LAYOUT`` (several may be
+given) the kernels are csrc/yuv_layout.hip's and the yardstick is the planar
+4:2:0 kernel of the same depth, matrix and range: 12 + 1.5 / 2 / 3 samples' bytes
+per pixel at 4:2:0 / 4:2:2 / 4:4:4."""
 import argparse
 import json
 import os
@@ -132,27 +137,35 @@ def kernel_block(device, frames, splats, reps, seconds):
 
 
 def format_block(device, fmt, frames, splats, reps, seconds):
-    """The kernels of ``fmt`` against the legacy ones, in one session."""
+    """The kernels of ``fmt`` against their yardstick, in one session: the legacy
+    8-bit kernels for a planar 4:2:0 format, the planar 4:2:0
+    kernels of the same colour triple for any other chroma or layout (§13f)."""
     from gsvc_amd import _lib as L
     xyz, chol, feat = gop_inputs(device, frames, splats)
     bound = torch.tensor([0.5, 0.0, 0.5], device=device)
     bg = torch.ones(3, device=device)
     sizes = [splats] * frames
-    sb = fmt.sample_bytes
+    yard = None if fmt.is_planar420 else YuvFormat(fmt.bit_depth, fmt.matrix, fmt.full_range)
+    yname = "legacy" if fmt.is_planar420 else "planar420"
+
+    def sample_bytes_per_pixel(f):
+        return 1.5 if f is None else f.frame_bytes(H, W) / (H * W)
 
     def render():
         return render_frames_sum(xyz, chol, feat, sizes, H, W, bg, cholesky_bound=bound)
 
-    res = {"format": str(fmt), "frames": frames, "splats": splats}
-    behind = compare({"render_legacy": lambda: rgb_to_i420(render()),
+    res = {"format": str(fmt), "pix_fmt": fmt.pix_fmt, "yardstick": "legacy 8-bit I420" if yard is None else str(yard),
+           "frames": frames, "splats": splats}
+    behind = compare({"render_" + yname: lambda: rgb_to_i420(render(), fmt=yard),
                       "render_format": lambda: rgb_to_i420(render(), fmt=fmt)}, reps, seconds)
-    behind["ratio"] = round(behind["render_format"]["median_us"] / behind["render_legacy"]["median_us"], 4)
+    behind["ratio"] = round(behind["render_format"]["median_us"] / behind["render_" + yname]["median_us"], 4)
     res["behind_render"] = behind
 
     # alone: three batches of images (600 MB: past the Infinity Cache) and their references
     base = render()
     batches = [base, (base * 0.5).contiguous(), (1.0 - base).contiguous()]
-    refs = {None: [rgb_to_i420(b.flip(0)) for b in batches], fmt: [rgb_to_i420(b.flip(0), fmt=fmt) for b in batches]}
+    refs = {yard: [rgb_to_i420(b.flip(0), fmt=yard) for b in batches],
+            fmt: [rgb_to_i420(b.flip(0), fmt=fmt) for b in batches]}
     turn = [0]
 
     def convert(f, with_ref):
@@ -169,41 +182,55 @@ def format_block(device, fmt, frames, splats, reps, seconds):
                              share_of_copy_rate=round(rate / PEAK_COPY, 3),
                              us_per_frame=round(got[name]["median_us"] / count, 3))
 
-    out = compare({"legacy": convert(None, False), "format": convert(fmt, False)}, reps, seconds)
-    rates(out, (("legacy", 13.5, frames), ("format", 12 + 1.5 * sb, frames)))
-    out["rate_ratio"] = round(out["format"]["tb_per_s"] / out["legacy"]["tb_per_s"], 4)
+    by, bf = sample_bytes_per_pixel(yard), sample_bytes_per_pixel(fmt)
+    out = compare({yname: convert(yard, False), "format": convert(fmt, False)}, reps, seconds)
+    rates(out, ((yname, 12 + by, frames), ("format", 12 + bf, frames)))
+    out["rate_ratio"] = round(out["format"]["tb_per_s"] / out[yname]["tb_per_s"], 4)
     res["output"] = out
-    out = compare({"legacy": convert(None, True), "format": convert(fmt, True)}, reps, seconds)
-    rates(out, (("legacy", 15.0, frames), ("format", 12 + 3.0 * sb, frames)))
-    out["rate_ratio"] = round(out["format"]["tb_per_s"] / out["legacy"]["tb_per_s"], 4)
+    out = compare({yname: convert(yard, True), "format": convert(fmt, True)}, reps, seconds)
+    rates(out, ((yname, 12 + 2 * by, frames), ("format", 12 + 2 * bf, frames)))
+    out["rate_ratio"] = round(out["format"]["tb_per_s"] / out[yname]["tb_per_s"], 4)
     res["output_ref"] = out
 
     # input, one frame per call as load_yuv_frames does; 16 output slots (400 MB) in rotation
     slots = [torch.empty((1, 3, H, W), dtype=torch.float32, device=device) for _ in range(16)]
-    raw8 = refs[None][0]
-    rawf = refs[fmt][0]
-    c_fmt, stream = fmt._c(), L.stream(device)
+    stream = L.stream(device)
 
-    def legacy_in():
-        turn[0] = (turn[0] + 1) % 16
-        L.call("gsvc_i420_to_rgb", L.ptr(raw8[turn[0] % frames]), H, W, L.ptr(slots[turn[0]]), stream)
+    def input_call(f):
+        raw = refs[f][0]
+        if f is None or f.is_legacy:
+            def run():
+                turn[0] = (turn[0] + 1) % 16
+                L.call("gsvc_i420_to_rgb", L.ptr(raw[turn[0] % frames]), H, W, L.ptr(slots[turn[0]]), stream)
+        elif f.is_planar420:
+            c_fmt = f._c()
 
-    def format_in():
-        turn[0] = (turn[0] + 1) % 16
-        L.call("gsvc_yuv420_to_rgb", 1, L.ptr(rawf[turn[0] % frames]), H, W, c_fmt, L.ptr(slots[turn[0]]), stream)
+            def run():
+                turn[0] = (turn[0] + 1) % 16
+                L.call("gsvc_yuv420_to_rgb", 1, L.ptr(raw[turn[0] % frames]), H, W, c_fmt, L.ptr(slots[turn[0]]),
+                       stream)
+        else:
+            c_fmt, chroma, semi = f._c(), int(f.chroma), int(f.layout == "semi")
 
-    out = compare({"legacy": legacy_in, "format": format_in}, reps, seconds)
-    rates(out, (("legacy", 13.5, 1), ("format", 12 + 1.5 * sb, 1)))
-    out["rate_ratio"] = round(out["format"]["tb_per_s"] / out["legacy"]["tb_per_s"], 4)
+            def run():
+                turn[0] = (turn[0] + 1) % 16
+                L.call("gsvc_yuv_to_rgb", 1, L.ptr(raw[turn[0] % frames]), H, W, c_fmt, chroma, semi,
+                       L.ptr(slots[turn[0]]), stream)
+        return run
+
+    out = compare({yname: input_call(yard), "format": input_call(fmt)}, reps, seconds)
+    rates(out, ((yname, 12 + by, 1), ("format", 12 + bf, 1)))
+    out["rate_ratio"] = round(out["format"]["tb_per_s"] / out[yname]["tb_per_s"], 4)
     res["input"] = out
     return res
 
 
 def _parse_format(text):
-    depth, matrix, rng = text.split(":")
-    if rng not in ("limited", "full"):
-        raise SystemExit("--format is DEPTH:MATRIX:limited|full, e.g. 10:bt709:limited")
-    return YuvFormat(int(depth), matrix, rng == "full")
+    parts = text.split(":")
+    if len(parts) not in (3, 5) or parts[2] not in ("limited", "full"):
+        raise SystemExit("--format is DEPTH:MATRIX:limited|full[:CHROMA:LAYOUT], e.g. 10:bt709:limited or "
+                         "10:bt709:limited:422:planar")
+    return YuvFormat(int(parts[0]), parts[1], parts[2] == "full", *parts[3:])
 
 
 def _host_i420(rgb):
@@ -291,8 +318,10 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.2, help="seconds per timed window")
-    ap.add_argument("--format", default=None, metavar="DEPTH:MATRIX:RANGE",
-                    help="measure this pixel format's kernels against the legacy ones instead, e.g. 10:bt709:limited")
+    ap.add_argument("--format", default=None, metavar="DEPTH:MATRIX:RANGE[:CHROMA:LAYOUT]", nargs="+",
+                    help="measure these pixel formats' kernels against their yardstick instead, e.g. "
+                         "10:bt709:limited (against the legacy kernels) or 10:bt709:limited:422:planar "
+                         "(against planar 4:2:0 of the same depth)")
     ap.add_argument("--tmp", default="/dev/shm" if os.path.isdir("/dev/shm") else None,
                     help="where the end-to-end files go (tmpfs)")
     args = ap.parse_args(argv)
@@ -302,13 +331,14 @@ def main(argv=None):
     line = {"device": torch.cuda.get_device_name(0), "H": H, "W": W, "reps": args.reps,
             "window_s": args.window, "kernels": [], "end_to_end": []}
     if args.format:
-        fmt = _parse_format(args.format)
+        fmts = [_parse_format(text) for text in args.format]
         del line["kernels"], line["end_to_end"]
         line["formats"] = []
         with torch.no_grad():
-            for splats in args.splats:
-                line["formats"].append(format_block(device, fmt, args.frames, splats, args.reps, args.window))
-                print(json.dumps(line["formats"][-1]), flush=True)
+            for fmt in fmts:
+                for splats in args.splats:
+                    line["formats"].append(format_block(device, fmt, args.frames, splats, args.reps, args.window))
+                    print(json.dumps(line["formats"][-1]), flush=True)
         return _write(line, args.out)
     with torch.no_grad():
         for splats in args.splats:
