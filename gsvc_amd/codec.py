@@ -12,6 +12,7 @@ csrc/yuv_layout.hip), and is the command line of the three steps:
     python -m gsvc_amd.codec encode MODELS.pth SRC.yuv OUT.gsvf --width W --height H
     python -m gsvc_amd.codec info OUT.gsvf
     python -m gsvc_amd.codec decode OUT.gsvf OUT.yuv [--reference SRC.yuv]
+                                    [--size WxH] [--crop X,Y,W,H]
 
 Not part of the reference, which writes PNG images and an MP4 through OpenCV
 (train_video_Compress.py) and has no bitstream file.
@@ -214,7 +215,7 @@ def _psnr(sse: int, count: int, peak: int = 255) -> float:
 
 
 def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Optional[range] = None,
-                 reference=None, fmt: Optional[YuvFormat] = None) -> dict:
+                 reference=None, fmt: Optional[YuvFormat] = None, size=None, crop=None) -> dict:
     """Decode a container file (a path) or a list of frame streams to YUV
     (planar 4:2:0 unless the format says otherwise), appended frame by frame to ``out_path`` (a raw .yuv; nothing
     is written when None).  ``fmt``: the output's pixel format; None means the
@@ -237,7 +238,13 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
     per-frame ``psnr_y / psnr_u / psnr_v`` (peak 2^bit_depth - 1, from the kernel's
     exact integer SSE, float64 on the host; inf for identical planes) and
     ``psnr_yuv`` = (6 Y + U + V) / 8.  Returns {"frames", "bytes_written",
-    "seconds" (host clock, ending in a synchronise), and the PSNR lists}."""
+    "seconds" (host clock, ending in a synchronise), "height", "width" (of the
+    frames written), and the PSNR lists}.
+
+    ``size=(H2, W2)`` and ``crop=(x0, y0, w, h)`` decode at another size and
+    window (``decode_frames``: the models sampled at the view's positions, no
+    prefilter): the frames written, the pinned buffers and ``bytes_written``
+    follow H2 x W2, and ``reference`` needs the identity view."""
     vid = read_video(src) if isinstance(src, (str, os.PathLike)) else _video_of_streams(src)
     device = torch.device(device)
     batch = int(batch)
@@ -248,6 +255,14 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
         raise ValueError(f"frames must be a range(a, b) with 0 <= a < b <= {vid.num_frames}")
     H, W = vid.H, vid.W
     fmt = fmt or vid.format
+    view, view_size = None, size  # (``size`` below: a frame's bytes)
+    if size is not None or crop is not None:
+        from .render import view_of
+        view = view_of(H, W, size, crop)
+        if reference is not None and not view.is_identity:
+            raise ValueError("decode_video: reference frames have the source's size; a view that is not "
+                             "the identity cannot be compared with them")
+        H, W = view.out_h, view.out_w  # the output's: what is checked, sized and written below
     if fmt.is_planar420 and (H % 2 or W % 2):
         raise ValueError(f"I420 needs an even height and width, not {H}x{W}")
     fmt.check_size(H, W)  # 4:2:2: W even; 4:4:4: any size
@@ -291,8 +306,12 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
             ref = None
             if mm is not None:
                 ref = torch.from_numpy(np.array(mm[s * size:e * size])).to(device)
-            out, state = decode_frames(streams, device, prev=state, return_state=True, output="i420",
-                                       reference=ref, fmt=fmt)
+            if view is None:
+                out, state = decode_frames(streams, device, prev=state, return_state=True, output="i420",
+                                           reference=ref, fmt=fmt)
+            else:
+                out, state = decode_frames(streams, device, prev=state, return_state=True, output="i420",
+                                           reference=ref, fmt=fmt, size=view_size, crop=crop)
             sse = None
             if ref is not None:
                 out, sse = out
@@ -323,7 +342,7 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
     finally:
         if fh is not None:
             fh.close()
-    res = {"frames": b - a, "bytes_written": written, "seconds": seconds}
+    res = {"frames": b - a, "bytes_written": written, "seconds": seconds, "height": H, "width": W}
     if mm is not None:
         tot = np.concatenate(sse_rows).astype(np.int64)
         n, cn = H * W, math.prod(fmt.chroma_shape(H, W))
@@ -362,8 +381,22 @@ def _decode(args) -> dict:
     fmt = format_of_arguments(args)  # an override: on top of the file's own format
     if fmt is not None:
         fmt = format_of_arguments(args, read_video(args.file).format)
+    size = crop = None
+    if args.size:
+        try:
+            w, h = (int(v) for v in args.size.lower().split("x"))
+        except ValueError:
+            raise ValueError(f"--size is WxH, not {args.size!r}") from None
+        size = (h, w)
+    if args.crop:
+        try:
+            crop = tuple(float(v) for v in args.crop.split(","))
+        except ValueError:
+            crop = ()
+        if len(crop) != 4:
+            raise ValueError(f"--crop is X,Y,W,H, not {args.crop!r}")
     return decode_video(args.file, args.out, device=args.device, batch=args.batch, frames=frames,
-                        reference=args.reference, fmt=fmt)
+                        reference=args.reference, fmt=fmt, size=size, crop=crop)
 
 
 def _encode(args) -> dict:
@@ -401,6 +434,10 @@ def main(argv=None) -> dict:
     p.add_argument("--batch", type=int, default=8)
     p.add_argument("--frames", default=None, help="A:B, frames A <= i < B from 0 (default all)")
     p.add_argument("--reference", default=None, help="the source .yuv, in the output's format: per-frame PSNR")
+    p.add_argument("--size", default=None, metavar="WxH",
+                   help="the output's size (default the file's): the models sampled at that grid, no prefilter")
+    p.add_argument("--crop", default=None, metavar="X,Y,W,H",
+                   help="a window of the frame in source pixels, fractions allowed (default the whole frame)")
     add_format_arguments(p)  # override the file's own format
     p.set_defaults(run=_decode)
     p = sub.add_parser("encode", help="overfit frame models + source .yuv -> container file")

@@ -832,7 +832,7 @@ def unpack_frames(streams: Sequence[bytes], device, cholesky_bound=None, prev=No
 
 
 def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: bool = False,
-                  output: str = "rgb", reference=None, fmt=None):
+                  output: str = "rgb", reference=None, fmt=None, size=None, crop=None):
     """Frame streams (``encode_frame``, either version, in any mix) to images
     [F, 3, H, W], or with ``output="i420"`` (or, beside a ``fmt``, its synonym
     ``"yuv"``) to YUV
@@ -846,7 +846,17 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
     ``render_frames_sum``.  A delta frame adds the DECODED parameters of the
     frame before it; ``prev`` carries them from an earlier call
     (``return_state=True`` also returns (xq, Lpre, cq) of the last frame).
-    CPU: the numpy decoder and the CPU operators, frame by frame."""
+    CPU: the numpy decoder and the CPU operators, frame by frame.
+
+    ``size=(H2, W2)`` and ``crop=(x0, y0, w, h)`` (source pixels, fractions
+    allowed) decode through a ``render.View``: the frame models, functions of
+    position, sampled at the view's positions -- images [F, 3, H2, W2], and
+    ``output="i420"`` / ``fmt`` at H2 x W2.  Unpacking, ``prev`` and the
+    returned state are the source's and do not depend on the view.  A view
+    that is not the identity cannot take ``reference`` frames (they have the
+    source's size): ValueError, as for a window outside the frame, a
+    non-positive size or a size the pixel format does not allow.  On the CPU
+    the view goes through the CPU statement of the resampled forward."""
     device = torch.device(device)
     if output not in ("rgb", "i420", "yuv"):
         raise ValueError(f"decode_frames: output is 'rgb', 'i420' or 'yuv', not {output!r}")
@@ -860,10 +870,25 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
         raise ValueError("decode_frames: a pixel format applies to output='i420'")
     if len(streams) == 0:
         raise ValueError("decode_frames: no frames")
+    view = None
+    if size is not None or crop is not None:
+        from .render import view_of
+        h0 = parse_header(streams[0])
+        view = view_of(h0["H"], h0["W"], size, crop)  # ValueError: the window, the size
+        if reference is not None and not view.is_identity:
+            raise ValueError("decode_frames: reference frames have the source's size; a view that is "
+                             "not the identity cannot be compared with them")
+        if output == "i420":
+            from .video import YuvFormat
+            (fmt or YuvFormat()).check_size(view.out_h, view.out_w)
     if device.type == "cuda":
         xq, Lq, cq, Lpre, sizes, (H, W) = unpack_frames(streams, device, prev=prev)
         bg = torch.ones(3, device=device)
-        imgs = render_frames_sum(xq, Lq, cq, sizes, H, W, bg, xyz_tanh=True, cholesky_bound=None)
+        if view is None:
+            imgs = render_frames_sum(xq, Lq, cq, sizes, H, W, bg, xyz_tanh=True, cholesky_bound=None)
+        else:
+            imgs = render_frames_sum(xq, Lq, cq, sizes, H, W, bg, xyz_tanh=True, cholesky_bound=None,
+                                     view=view)
         last = sum(sizes[:-1])
         state = (xq[last:], Lpre[last:], cq[last:])
     else:
@@ -875,6 +900,12 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
         imgs = []
         for xq, Lq, cq, _ in frames:
             n = xq.shape[0]
+            if view is not None:
+                from .cpu import render_sum_resampled
+                imgs.append(render_sum_resampled(torch.tanh(torch.from_numpy(xq)), torch.from_numpy(Lq),
+                                                 torch.from_numpy(cq), torch.ones(n, 1), torch.ones(3),
+                                                 view))
+                continue
             xys, depths, radii, conics, nth = project_gaussians_2d(
                 torch.tanh(torch.from_numpy(xq)), torch.from_numpy(Lq), H, W, tb)
             img = rasterize_gaussians_sum(xys, depths, radii, conics, nth, torch.from_numpy(cq),

@@ -35,6 +35,8 @@ _SIGS = {
     "gsvc_cpu_bin_tiles": ([_I, _P, _P, _I, _I, _P, _P], ctypes.c_longlong),
     "gsvc_cpu_rasterize_sum_forward": ([_I, _I, _U, _U, _P, _P, _P, _P, _P, _P, _P, _P], None),
     "gsvc_cpu_rasterize_sum_backward": ([_U, _U, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P], None),
+    "gsvc_cpu_rasterize_sum_resampled": ([_I, _I, _P, _P, _P, _P, _P, _P, ctypes.c_longlong, _P, _P, _P,
+                                          _P, _P, _U, _U, _P], _I),
 }
 _lib = None
 _lock = threading.Lock()
@@ -152,6 +154,36 @@ class RasterizeGaussiansSumCPU(Function):
         if opacity.dim() != 2:
             v_opac = v_opac.reshape(opacity.shape)
         return rec[:, 0:2], None, rec[:, 2:5], rec[:, 5:8], v_opac, None, None, None
+
+
+def render_sum_resampled(means2d, L_elements, colors, opacity, background, view):
+    """One frame model through a ``render.View`` on the CPU (no autograd): the
+    projection and the tile bins at the view's SOURCE size, then the sum
+    composite of each source tile's list at the view's sample positions
+    (gsvc_cpu_rasterize_sum_resampled) -- clamped planes [3, out_h, out_w].
+    The CPU statement of csrc/resample.hip."""
+    H, W = view.src_h, view.src_w
+    tbx, tby = (W + 15) // 16, (H + 15) // 16
+    with torch.no_grad():
+        xys, _, radii, conics, _ = ProjectGaussians2dCPU.apply(
+            _cpu(means2d.detach(), "means2d"), _cpu(L_elements.detach(), "L_elements"), H, W,
+            (tbx, tby, 1))
+        colors = _cpu(colors.detach(), "colors")
+        opacity = _cpu(opacity.detach(), "opacity")
+        background = _cpu(background.detach(), "background")
+        n = xys.shape[0]
+        ids = torch.empty((tbx * tby * TILE_KEEP,), dtype=torch.int32)
+        bins = torch.empty((tbx * tby, 2), dtype=torch.int32)
+        m = lib().gsvc_cpu_bin_tiles(n, _p(xys), _p(radii), tbx, tby, _p(ids), _p(bins))
+        out = torch.empty((3, view.out_h, view.out_w))
+        sx, sy, cs, rs = view.host_tables()
+        rc = lib().gsvc_cpu_rasterize_sum_resampled(
+            tbx, tby, _p(ids), _p(bins), _p(xys), _p(conics), _p(colors), _p(opacity), int(m),
+            _p(background), sx.ctypes.data, sy.ctypes.data, cs.ctypes.data, rs.ctypes.data,
+            view.out_h, view.out_w, _p(out))
+    if rc != 0:
+        raise RuntimeError("gsvc_cpu_rasterize_sum_resampled: the view's tables do not partition its output")
+    return out
 
 
 def project_gaussians_2d(means2d, L_elements, img_height, img_width, tile_bounds, clip_thresh=0.01):

@@ -209,6 +209,63 @@ void gsvc_cpu_rasterize_sum_forward(int tbx, int tby, unsigned img_w, unsigned i
     }
 }
 
+// The sum composite at the sample positions of a view (csrc/resample.hip,
+// include/gsvc_amd.h gsvc_render_frames_resampled; not part of the reference):
+// source tile t's entry list against the output samples it owns -- rows
+// [row_start[ty], row_start[ty + 1]) x columns [col_start[tx],
+// col_start[tx + 1]) -- at (sample_x[j'], sample_y[i']) where the forward
+// above has ((float)px, (float)py); out [3, out_h, out_w] clamped to [0, 1]
+// (NaN kept).  m < 1 (no intersections): the clamped background.  Returns 0,
+// or -1 when the start tables do not partition the output (nothing written).
+int gsvc_cpu_rasterize_sum_resampled(int tbx, int tby, const int *ids, const int *bins,
+                                     const float *xys, const float *conics, const float *colors,
+                                     const float *opac, long long m, const float *background,
+                                     const float *sample_x, const float *sample_y,
+                                     const int *col_start, const int *row_start, unsigned out_h,
+                                     unsigned out_w, float *out) {
+    const int W2 = (int)out_w, H2 = (int)out_h;
+    if (tbx < 1 || tby < 1 || W2 < 1 || H2 < 1 || col_start[0] != 0 || col_start[tbx] != W2 ||
+        row_start[0] != 0 || row_start[tby] != H2)
+        return -1;
+    for (int t = 0; t < tbx; ++t)
+        if (col_start[t + 1] < col_start[t]) return -1;
+    for (int t = 0; t < tby; ++t)
+        if (row_start[t + 1] < row_start[t]) return -1;
+    const size_t plane = (size_t)H2 * W2;
+    auto clamp01 = [](float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); };
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int t = 0; t < tbx * tby; ++t) {
+        const int ty = t / tbx, tx = t - ty * tbx;
+        const int b0 = bins[2 * t], b1 = m < 1 ? b0 : std::min(bins[2 * t + 1], b0 + kKeep);
+        for (int oi = row_start[ty]; oi < row_start[ty + 1]; ++oi)
+            for (int oj = col_start[tx]; oj < col_start[tx + 1]; ++oj) {
+                const float px = sample_x[oj], py = sample_y[oi];
+                float r = 0.f, g = 0.f, b = 0.f;
+                if (m < 1) {
+                    r = background[0];
+                    g = background[1];
+                    b = background[2];
+                }
+                for (int k = b0; k < b1; ++k) {
+                    const int s = ids[k];
+                    const float dx = xys[2 * s] - px, dy = xys[2 * s + 1] - py;
+                    const float sg = sigma_of(0.5f * conics[3 * s], conics[3 * s + 1],
+                                              0.5f * conics[3 * s + 2], dx, dy);
+                    const float al = fminf(1.0f, opac[s] * exp2f(sg * kNegLog2e));
+                    if (sg < 0.0f || al < kAlphaMin) continue;
+                    r = fmaf(colors[3 * s], al, r);
+                    g = fmaf(colors[3 * s + 1], al, g);
+                    b = fmaf(colors[3 * s + 2], al, b);
+                }
+                const size_t p = (size_t)oi * W2 + oj;
+                out[p] = clamp01(r);
+                out[plane + p] = clamp01(g);
+                out[2 * plane + p] = clamp01(b);
+            }
+    }
+    return 0;
+}
+
 // backward.cu:696-862 into grad [N, 16] (v_xy 0:2, v_conic 2:5, v_colors
 // 5:8, v_opacity 8), zeroed here: every (pixel, entry k <= final_idx) pair
 // passing the forward's test, in tile order then pixel order (one thread per

@@ -18,6 +18,10 @@ Results are bit-identical to the autograd path (tests/test_gpu_sync_free.py).
 
 ``render_sum_frame`` is the same for already-activated inputs (means2d, L,
 colors, opacity), the signature of the two reference ops it replaces.
+
+``render_frames_sum`` renders a batch of frame models in one call, and with a
+``View`` (an output size and a window of the frame) at other sample positions:
+gsvc_render_frames_resampled, csrc/resample.hip, DESIGN.md §13g.
 """
 from __future__ import annotations
 
@@ -236,18 +240,151 @@ class _BatchWorkspace:
 _batch_workspaces = {}
 
 
+def _axis_tables(src: int, out: int, start: float, extent: float):
+    """One axis of a view, float64 (include/gsvc_amd.h): the sample coordinates
+    xd, their owner pixels p, and the owner tiles' start table."""
+    import numpy as np
+    j = np.arange(out, dtype=np.float64)
+    xd = float(start) + ((2.0 * j + 1.0) * float(extent)) / (2.0 * float(out)) - 0.5
+    p = np.minimum(np.maximum(np.floor(xd + 0.5), 0.0), float(src - 1)).astype(np.int64)
+    tiles = (src + 15) // 16
+    starts = np.searchsorted(p >> 4, np.arange(tiles + 1), side="left").astype(np.int32)
+    return xd, p, starts
+
+
+class View:
+    """An output size and window of a frame model of ``src_h`` x ``src_w``:
+    ``size=(H2, W2)`` (default: the source's) and ``crop=(x0, y0, w, h)`` in
+    source pixels, fractions allowed (default: the whole frame).  Source pixel
+    j is the sample at the centre of [j, j + 1), so output column j' is
+    evaluated at ``x0 + ((2 j' + 1) w) / (2 W2) - 0.5`` with the entry list of
+    the source tile that owns that position (include/gsvc_amd.h
+    gsvc_render_frames_resampled).  ValueError for a window outside the frame
+    or a non-positive size.  ``out_h``, ``out_w``, ``is_identity``; the four
+    tables as numpy arrays (``host_tables``) and, cached per device, as tensors
+    (``device_tables``).  Views point-sample: a downscale aliases where splats
+    are smaller than an output pixel (average an odd-factor upscale to
+    supersample)."""
+
+    def __init__(self, src_h: int, src_w: int, size=None, crop=None):
+        import numpy as np
+        self.src_h, self.src_w = int(src_h), int(src_w)
+        if self.src_h < 1 or self.src_w < 1:
+            raise ValueError(f"View: the source is {src_h}x{src_w}")
+        if size is None:
+            size = (self.src_h, self.src_w)
+        try:
+            h2, w2 = size
+            ok = int(h2) == h2 and int(w2) == w2
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok or h2 < 1 or w2 < 1:
+            raise ValueError(f"View: size is (H2, W2), both integers >= 1, not {size!r}")
+        self.out_h, self.out_w = int(h2), int(w2)
+        if crop is None:
+            crop = (0, 0, self.src_w, self.src_h)
+        try:
+            x0, y0, w, h = (float(v) for v in crop)
+        except (TypeError, ValueError):
+            raise ValueError(f"View: crop is (x0, y0, w, h), not {crop!r}") from None
+        if not (0.0 <= x0 and w > 0.0 and x0 + w <= self.src_w and 0.0 <= y0 and h > 0.0
+                and y0 + h <= self.src_h):
+            raise ValueError(f"View: crop {crop!r} is no window inside the {self.src_w}x{self.src_h} frame "
+                             "(0 <= x0, w > 0, x0 + w <= W; rows alike)")
+        self.crop = (x0, y0, w, h)
+        self.is_identity = ((self.out_h, self.out_w) == (self.src_h, self.src_w)
+                            and self.crop == (0.0, 0.0, float(self.src_w), float(self.src_h)))
+        self.xd, self.px, col_start = _axis_tables(self.src_w, self.out_w, x0, w)
+        self.yd, self.py, row_start = _axis_tables(self.src_h, self.out_h, y0, h)
+        self.sample_x = np.ascontiguousarray(self.xd.astype(np.float32))
+        self.sample_y = np.ascontiguousarray(self.yd.astype(np.float32))
+        self.col_start = np.ascontiguousarray(col_start)
+        self.row_start = np.ascontiguousarray(row_start)
+        self._device = {}
+
+    def host_tables(self):
+        """(sample_x float32 [W2], sample_y float32 [H2], col_start int32
+        [tbx + 1], row_start int32 [tby + 1])."""
+        return self.sample_x, self.sample_y, self.col_start, self.row_start
+
+    def device_tables(self, device):
+        key = (device.type, device.index)
+        t = self._device.get(key)
+        if t is None:
+            t = self._device[key] = tuple(torch.from_numpy(a).to(device) for a in self.host_tables())
+        return t
+
+
+_views = {}
+
+
+def view_of(src_h: int, src_w: int, size=None, crop=None) -> View:
+    """``View(src_h, src_w, size, crop)``, kept for the next call with the
+    same arguments (a decoder asks once per batch)."""
+    try:
+        key = (int(src_h), int(src_w), None if size is None else tuple(size),
+               None if crop is None else tuple(crop))
+        hash(key)
+    except TypeError:
+        return View(src_h, src_w, size, crop)  # (its ValueError)
+    v = _views.get(key)
+    if v is None:
+        if len(_views) >= 64:
+            _views.clear()
+        v = _views[key] = View(src_h, src_w, size, crop)
+    return v
+
+
+def _render_frames_view_cpu(xyz, cholesky, features, sizes, background, xyz_tanh, cholesky_bound,
+                            rgb_w, opacity, view: View) -> Tensor:
+    """render_frames_sum(view=) for CPU tensors: frame by frame through the
+    CPU statement of the resampled forward (cpu.render_sum_resampled)."""
+    from .cpu import render_sum_resampled
+    imgs, a = [], 0
+    for n in sizes:
+        sl = slice(a, a + n)
+        a += n
+        means = xyz[sl].detach().float()
+        if xyz_tanh:
+            means = torch.tanh(means)
+        chol = cholesky[sl].detach().float()
+        if cholesky_bound is not None:
+            chol = chol + cholesky_bound.detach().float().reshape(1, 3)
+        col = features[sl].detach().float()
+        if rgb_w is not None:
+            col = col * rgb_w[sl].detach().float().reshape(n, 1)
+        opac = torch.ones(n, 1) if opacity is None else opacity[sl].detach().float().reshape(n, 1)
+        imgs.append(render_sum_resampled(means, chol, col, opac, background.detach().float(), view))
+    return torch.stack(imgs).contiguous()
+
+
 def render_frames_sum(xyz: Tensor, cholesky: Tensor, features: Tensor, frame_sizes,
                       img_height: int, img_width: int, background: Tensor, xyz_tanh: bool = True,
                       cholesky_bound: Optional[Tensor] = None, rgb_w: Optional[Tensor] = None,
-                      opacity: Optional[Tensor] = None) -> Tensor:
+                      opacity: Optional[Tensor] = None, view: Optional[View] = None) -> Tensor:
     """Render a batch of frame models of one video in one call (two kernels
     over all frames; gsvc_render_frames_sum): the inputs are the frames'
     splats concatenated (frame b has ``frame_sizes[b]`` of them, in order),
     the output [F, 3, H, W] -- each image bit-identical to
     ``render_frame_sum`` of that frame alone.  A video decoder's GOP: GSVC
-    stores one model per frame (train_video_Represent.py:379-384)."""
+    stores one model per frame (train_video_Represent.py:379-384).
+
+    ``view`` (a ``View`` of this H x W): the frames at the view's size and
+    window, [F, 3, view.out_h, view.out_w], through
+    gsvc_render_frames_resampled -- the same projection and per-tile lists,
+    composited at the view's sample positions (an identity view takes that
+    kernel too, and gives the bits of ``view=None``).  With a view, CPU tensors
+    go through the CPU statement of the same forward."""
     import ctypes
     H, W = int(img_height), int(img_width)
+    if view is not None and (view.src_h, view.src_w) != (H, W):
+        raise ValueError(f"the view is of a {view.src_h}x{view.src_w} frame, the models' is {H}x{W}")
+    if view is not None and not xyz.is_cuda:
+        sizes = [int(x) for x in frame_sizes]
+        if len(sizes) < 1 or any(x < 0 for x in sizes) or sum(sizes) != xyz.shape[0]:
+            raise ValueError("frame_sizes must be non-negative counts that sum to the inputs' splats")
+        return _render_frames_view_cpu(xyz, cholesky, features, sizes, background, xyz_tanh,
+                                       cholesky_bound, rgb_w, opacity, view)
     sizes = [int(x) for x in frame_sizes]
     F = len(sizes)
     if F < 1 or any(x < 0 for x in sizes):
@@ -285,6 +422,25 @@ def render_frames_sum(xyz: Tensor, cholesky: Tensor, features: Tensor, frame_siz
     if bw.offs_host is None or list(bw.offs_host) != offs:
         bw.offs_host = (ctypes.c_int * (F + 1))(*offs)
         bw.offs = torch.tensor(offs, dtype=torch.int32, device=dev)
+    if view is not None:
+        # the same workspace and call parity as the native entry: both leave
+        # the counts of the other parity zero
+        host = view.host_tables()
+        tabs = view.device_tables(dev)
+        out = torch.empty((F, 3, view.out_h, view.out_w), dtype=torch.float32, device=dev)
+        rc = L.load().gsvc_render_frames_resampled(
+            F, bw.offs_host, bw.offs.data_ptr(), p_xyz, 1 if xyz_tanh else 0, p_chol, p_bound, p_feat,
+            p_rgbw, p_opac, p_bg, H, W, bw.call, bw.hint, bw.meta.data_ptr(), bw.buf.data_ptr(),
+            bw.buf.numel(), host[0].ctypes.data, host[1].ctypes.data, host[2].ctypes.data,
+            host[3].ctypes.data, tabs[0].data_ptr(), tabs[1].data_ptr(), tabs[2].data_ptr(),
+            tabs[3].data_ptr(), view.out_h, view.out_w, out.data_ptr(), stream_handle)
+        if rc != 0:
+            bw.key = None
+            msg = L.load().gsvc_last_error().decode(errors="replace")
+            raise RuntimeError(f"gsvc_render_frames_resampled failed (status {rc}): {msg}")
+        bw.call += 1
+        bw.update_hint()
+        return out
     out = torch.empty((F, 3, H, W), dtype=torch.float32, device=dev)
     rc = L.load().gsvc_render_frames_sum(
         F, bw.offs_host, bw.offs.data_ptr(), p_xyz, 1 if xyz_tanh else 0, p_chol, p_bound, p_feat,

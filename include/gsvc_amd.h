@@ -584,6 +584,53 @@ int gsvc_render_frames_sum(int frames, const int *frame_offsets_host,
                            int call_index, int density_hint, int *meta, void *workspace,
                            size_t workspace_bytes, float *out, void *stream);
 
+/* The same batch of frame models at another output size and window (a view;
+ * not part of the reference): out [frames,3,out_h,out_w].  A frame model is a
+ * function of position -- per 16x16 tile of the SOURCE grid, the tile's first
+ * <= 256 entries in splat-id order -- which the native render samples at the
+ * integer coordinates (j, i).  Source pixel j is the sample at the centre of
+ * [j, j + 1) (half-pixel centres, as swscale and align_corners=False), so a
+ * view of the window x0, y0, w, h (source pixels, fractions allowed,
+ * 0 <= x0, w > 0, x0 + w <= W; rows alike) at out_h x out_w evaluates output
+ * column j' at, in float64 and in this order,
+ *     xd[j'] = x0 + ((2 j' + 1) w) / (2 out_w) - 0.5
+ * with the entry list of the tile that owns source pixel
+ *     p[j'] = min(max(floor(xd[j'] + 0.5), 0), W - 1),   tile p[j'] >> 4.
+ * The four tables, per axis (columns; rows alike with y, h, out_h, H, tby):
+ *     sample_x  float[out_w]   (float)xd[j']
+ *     col_start int[tbx + 1]   the number of j' whose owner tile is below t:
+ *                              p is monotone, so tile column t owns the output
+ *                              columns [col_start[t], col_start[t + 1]), a
+ *                              possibly empty range; the ranges partition
+ *                              [0, out_w)
+ * given as host and device copies (as frame_offsets): GSVC_ERR_ARG before any
+ * launch unless col_start[0] = 0, col_start[tbx] = out_w and col_start is
+ * non-decreasing (rows alike), every sample lies in [-1, W] x [-1, H], every
+ * buffer is there and out_h, out_w >= 1.  The rule is exact where it matters:
+ * the identity view has xd = j' (the native render's bits), an integer window
+ * at scale 1 xd = x0 + j' (the native render's window), and an odd integer
+ * upscale k puts output column k j + (k - 1) / 2 at x0 + j.  Other views
+ * point-sample the trained function: no prefilter, so a downscale aliases
+ * where splats are smaller than an output pixel.
+ * Projection, workspace, zeroed bytes, call_index parity and meta are those of
+ * gsvc_render_frames_sum at the source size img_height x img_width (one
+ * workspace may serve both entries); density_hint is accepted and unused.
+ * One composite wave per (frame, source tile) evaluates the tile's samples
+ * with the rasterizer's op sequence at (sample_x[j'], sample_y[i']) and
+ * writes the clamped planes. */
+int gsvc_render_frames_resampled(int frames, const int *frame_offsets_host,
+                                 const int *frame_offsets_dev, const float *xyz, int xyz_tanh,
+                                 const float *cholesky, const float *cholesky_bound,
+                                 const float *features, const float *rgb_w, const float *opacity,
+                                 const float *background, unsigned img_height, unsigned img_width,
+                                 int call_index, int density_hint, int *meta, void *workspace,
+                                 size_t workspace_bytes, const float *sample_x_host,
+                                 const float *sample_y_host, const int *col_start_host,
+                                 const int *row_start_host, const float *sample_x_dev,
+                                 const float *sample_y_dev, const int *col_start_dev,
+                                 const int *row_start_dev, unsigned out_h, unsigned out_w,
+                                 float *out, void *stream);
+
 /* Replaces _C.rasterize_sum_backward (bindings.cu:706-779 -> backward.cu:696-862).
  * Gradients are written into one 64-byte record per splat,
  * grad_records [N,16] float: [0:2] v_xy, [2:5] v_conic, [5:8] v_colors,
