@@ -115,6 +115,9 @@ _SIGS = {
                                _SZ, _P, _P],
     "gsvc_render_frames_resampled": [_I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _U, _U, _I, _I, _P,
                                      _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _U, _U, _P, _P],
+    "gsvc_render_frames_filtered": [_I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _U, _U, _I, _I, _P,
+                                    _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _U, _U, _U, _U, _P, _SZ,
+                                    _P, _P],
     "gsvc_adan_step": [_I, _P, _P, _P, _P, _P, _P, _P] + [ctypes.c_double] * 9 +
                       [_I, ctypes.c_double, _P],
     "gsvc_rasterize_sum_backward": [_U, _U, _U, _U, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,

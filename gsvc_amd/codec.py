@@ -12,7 +12,7 @@ csrc/yuv_layout.hip), and is the command line of the three steps:
     python -m gsvc_amd.codec encode MODELS.pth SRC.yuv OUT.gsvf --width W --height H
     python -m gsvc_amd.codec info OUT.gsvf
     python -m gsvc_amd.codec decode OUT.gsvf OUT.yuv [--reference SRC.yuv]
-                                    [--size WxH] [--crop X,Y,W,H]
+                                    [--size WxH] [--crop X,Y,W,H] [--aa auto|K|KYxKX]
 
 Not part of the reference, which writes PNG images and an MP4 through OpenCV
 (train_video_Compress.py) and has no bitstream file.
@@ -215,7 +215,7 @@ def _psnr(sse: int, count: int, peak: int = 255) -> float:
 
 
 def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Optional[range] = None,
-                 reference=None, fmt: Optional[YuvFormat] = None, size=None, crop=None) -> dict:
+                 reference=None, fmt: Optional[YuvFormat] = None, size=None, crop=None, aa=None) -> dict:
     """Decode a container file (a path) or a list of frame streams to YUV
     (planar 4:2:0 unless the format says otherwise), appended frame by frame to ``out_path`` (a raw .yuv; nothing
     is written when None).  ``fmt``: the output's pixel format; None means the
@@ -244,7 +244,9 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
     ``size=(H2, W2)`` and ``crop=(x0, y0, w, h)`` decode at another size and
     window (``decode_frames``: the models sampled at the view's positions, no
     prefilter): the frames written, the pinned buffers and ``bytes_written``
-    follow H2 x W2, and ``reference`` needs the identity view."""
+    follow H2 x W2, and ``reference`` needs the identity view.  ``aa`` (k,
+    (ky, kx) or "auto") adds the box prefilter of ``render.View``: every output
+    pixel the mean of ky x kx samples, reduced inside the composite."""
     vid = read_video(src) if isinstance(src, (str, os.PathLike)) else _video_of_streams(src)
     device = torch.device(device)
     batch = int(batch)
@@ -256,9 +258,9 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
     H, W = vid.H, vid.W
     fmt = fmt or vid.format
     view, view_size = None, size  # (``size`` below: a frame's bytes)
-    if size is not None or crop is not None:
+    if size is not None or crop is not None or aa is not None:
         from .render import view_of
-        view = view_of(H, W, size, crop)
+        view = view_of(H, W, size, crop, aa)
         if reference is not None and not view.is_identity:
             raise ValueError("decode_video: reference frames have the source's size; a view that is not "
                              "the identity cannot be compared with them")
@@ -311,7 +313,7 @@ def decode_video(src, out_path=None, device="cuda", batch: int = 8, frames: Opti
                                            reference=ref, fmt=fmt)
             else:
                 out, state = decode_frames(streams, device, prev=state, return_state=True, output="i420",
-                                           reference=ref, fmt=fmt, size=view_size, crop=crop)
+                                           reference=ref, fmt=fmt, size=view_size, crop=crop, aa=aa)
             sse = None
             if ref is not None:
                 out, sse = out
@@ -395,8 +397,17 @@ def _decode(args) -> dict:
             crop = ()
         if len(crop) != 4:
             raise ValueError(f"--crop is X,Y,W,H, not {args.crop!r}")
+    aa = None
+    if args.aa:
+        try:
+            k = () if args.aa == "auto" else tuple(int(v) for v in args.aa.lower().split("x"))
+        except ValueError:
+            k = (0, 0, 0)
+        if len(k) > 2:
+            raise ValueError(f"--aa is auto, K or KYxKX, not {args.aa!r}")
+        aa = "auto" if not k else k[0] if len(k) == 1 else k
     return decode_video(args.file, args.out, device=args.device, batch=args.batch, frames=frames,
-                        reference=args.reference, fmt=fmt, size=size, crop=crop)
+                        reference=args.reference, fmt=fmt, size=size, crop=crop, aa=aa)
 
 
 def _encode(args) -> dict:
@@ -438,6 +449,9 @@ def main(argv=None) -> dict:
                    help="the output's size (default the file's): the models sampled at that grid, no prefilter")
     p.add_argument("--crop", default=None, metavar="X,Y,W,H",
                    help="a window of the frame in source pixels, fractions allowed (default the whole frame)")
+    p.add_argument("--aa", default=None, metavar="auto|K|KYxKX",
+                   help="box prefilter: every output pixel the mean of KY x KX samples (auto: the downscale's "
+                        "factor per axis, at most 8)")
     add_format_arguments(p)  # override the file's own format
     p.set_defaults(run=_decode)
     p = sub.add_parser("encode", help="overfit frame models + source .yuv -> container file")

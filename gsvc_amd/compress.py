@@ -832,7 +832,7 @@ def unpack_frames(streams: Sequence[bytes], device, cholesky_bound=None, prev=No
 
 
 def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: bool = False,
-                  output: str = "rgb", reference=None, fmt=None, size=None, crop=None):
+                  output: str = "rgb", reference=None, fmt=None, size=None, crop=None, aa=None):
     """Frame streams (``encode_frame``, either version, in any mix) to images
     [F, 3, H, W], or with ``output="i420"`` (or, beside a ``fmt``, its synonym
     ``"yuv"``) to YUV
@@ -856,7 +856,13 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
     that is not the identity cannot take ``reference`` frames (they have the
     source's size): ValueError, as for a window outside the frame, a
     non-positive size or a size the pixel format does not allow.  On the CPU
-    the view goes through the CPU statement of the resampled forward."""
+    the view goes through the CPU statement of the resampled forward.
+
+    ``aa`` (k, (ky, kx) or "auto"; ``render.View``) box-filters the view inside
+    the composite, every output pixel the mean of ky x kx point samples: the
+    prefilter a downscale needs.  It may be given without ``size`` (a
+    supersampled image at the source's size); ``output="i420"`` and ``fmt``
+    apply to the filtered images."""
     device = torch.device(device)
     if output not in ("rgb", "i420", "yuv"):
         raise ValueError(f"decode_frames: output is 'rgb', 'i420' or 'yuv', not {output!r}")
@@ -871,10 +877,10 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
     if len(streams) == 0:
         raise ValueError("decode_frames: no frames")
     view = None
-    if size is not None or crop is not None:
+    if size is not None or crop is not None or aa is not None:
         from .render import view_of
         h0 = parse_header(streams[0])
-        view = view_of(h0["H"], h0["W"], size, crop)  # ValueError: the window, the size
+        view = view_of(h0["H"], h0["W"], size, crop, aa)  # ValueError: the window, the size, aa
         if reference is not None and not view.is_identity:
             raise ValueError("decode_frames: reference frames have the source's size; a view that is "
                              "not the identity cannot be compared with them")
@@ -901,10 +907,9 @@ def decode_frames(streams: Sequence[bytes], device, prev=None, return_state: boo
         for xq, Lq, cq, _ in frames:
             n = xq.shape[0]
             if view is not None:
-                from .cpu import render_sum_resampled
-                imgs.append(render_sum_resampled(torch.tanh(torch.from_numpy(xq)), torch.from_numpy(Lq),
-                                                 torch.from_numpy(cq), torch.ones(n, 1), torch.ones(3),
-                                                 view))
+                from .cpu import render_sum_view
+                imgs.append(render_sum_view(torch.tanh(torch.from_numpy(xq)), torch.from_numpy(Lq),
+                                            torch.from_numpy(cq), torch.ones(n, 1), torch.ones(3), view))
                 continue
             xys, depths, radii, conics, nth = project_gaussians_2d(
                 torch.tanh(torch.from_numpy(xq)), torch.from_numpy(Lq), H, W, tb)

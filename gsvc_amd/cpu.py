@@ -186,6 +186,54 @@ def render_sum_resampled(means2d, L_elements, colors, opacity, background, view)
     return out
 
 
+def box_reduce_view(fine_image, view):
+    """The box reduction of a view with ``aa = (ky, kx)``, as the rule states it
+    (include/gsvc_amd.h gsvc_render_frames_filtered): ``fine_image``
+    [..., ky H2, kx W2], the clamped image of ``view.fine``, to float32
+    [..., H2, W2].  Per output pixel the sub-samples (ky i' + a, kx j' + b) are
+    split by owner tile into up to 2 x 2 parts, slot = 2 (tile row - the first
+    sub-row's) + (tile column - the first sub-column's); each part is summed in
+    row-major (a, b) order from +0.0, the parts are added in slot order, and
+    the sum is divided by ky kx -- all in float32.  numpy, vectorised over the
+    pixels and sequential over (slot, a, b).  A tensor gives a tensor."""
+    import numpy as np
+    is_tensor = isinstance(fine_image, torch.Tensor)
+    fine = fine_image.detach().cpu().numpy() if is_tensor else np.asarray(fine_image)
+    fine = fine.astype(np.float32, copy=False)
+    ky, kx = view.aa
+    H2, W2 = view.out_h, view.out_w
+    if fine.shape[-2:] != (ky * H2, kx * W2):
+        raise ValueError(f"box_reduce_view: the image is {fine.shape[-2]}x{fine.shape[-1]}, the view's fine "
+                         f"view {ky * H2}x{kx * W2}")
+    tr = (view.fine.py >> 4).reshape(H2, ky)
+    tc = (view.fine.px >> 4).reshape(W2, kx)
+    dr, dc = tr - tr[:, :1], tc - tc[:, :1]  # 0 or 1: the tile after the first sub-sample's
+    total = None
+    for slot in range(4):
+        part = np.zeros(fine.shape[:-2] + (H2, W2), dtype=np.float32)
+        present = np.zeros((H2, W2), dtype=bool)
+        for a in range(ky):
+            for b in range(kx):
+                mask = (dr[:, a] == (slot >> 1))[:, None] & (dc[:, b] == (slot & 1))[None, :]
+                if mask.any():
+                    part = np.where(mask, part + fine[..., a::ky, b::kx], part)
+                    present |= mask
+        total = part if slot == 0 else np.where(present, total + part, total)
+    out = total / np.float32(ky * kx)
+    assert out.dtype == np.float32
+    return torch.from_numpy(np.ascontiguousarray(out)) if is_tensor else out
+
+
+def render_sum_view(means2d, L_elements, colors, opacity, background, view):
+    """``render_sum_resampled`` for any view: with ``aa``, the fine view's image
+    box-reduced (``box_reduce_view``) -- the CPU statement of
+    csrc/resample_aa.hip."""
+    if view.aa == (1, 1):
+        return render_sum_resampled(means2d, L_elements, colors, opacity, background, view)
+    return box_reduce_view(render_sum_resampled(means2d, L_elements, colors, opacity, background, view.fine),
+                           view)
+
+
 def project_gaussians_2d(means2d, L_elements, img_height, img_width, tile_bounds, clip_thresh=0.01):
     xys, depths, radii, conics, nth = ProjectGaussians2dCPU.apply(
         means2d, L_elements, img_height, img_width, tile_bounds, clip_thresh)

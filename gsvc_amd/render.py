@@ -21,7 +21,9 @@ colors, opacity), the signature of the two reference ops it replaces.
 
 ``render_frames_sum`` renders a batch of frame models in one call, and with a
 ``View`` (an output size and a window of the frame) at other sample positions:
-gsvc_render_frames_resampled, csrc/resample.hip, DESIGN.md §13g.
+gsvc_render_frames_resampled, csrc/resample.hip, DESIGN.md §13g.  A view with
+``aa`` box-filters inside the composite: gsvc_render_frames_filtered,
+csrc/resample_aa.hip, DESIGN.md §13h.
 """
 from __future__ import annotations
 
@@ -224,6 +226,7 @@ class _BatchWorkspace:
         self.hint = 0
         self.pinned = None
         self.event = None
+        self.parts = None  # the filtered composite's seam parts (gsvc_render_frames_filtered)
 
     def update_hint(self):
         if self.event is not None and self.event.query():
@@ -252,6 +255,27 @@ def _axis_tables(src: int, out: int, start: float, extent: float):
     return xd, p, starts
 
 
+def _aa_factors(aa, extent_h: float, out_h: int, extent_w: float, out_w: int):
+    """``aa`` of a view as (ky, kx): None, k, (ky, kx) or "auto" (per axis
+    min(8, max(1, ceil(extent / out))))."""
+    import math
+    if aa is None:
+        return 1, 1
+    if isinstance(aa, str):
+        if aa != "auto":
+            raise ValueError(f"View: aa is None, k, (ky, kx) or 'auto', not {aa!r}")
+        return (min(8, max(1, math.ceil(extent_h / out_h))), min(8, max(1, math.ceil(extent_w / out_w))))
+    try:
+        ky, kx = aa if isinstance(aa, (tuple, list)) else (aa, aa)
+        ok = int(ky) == ky and int(kx) == kx and ky >= 1 and kx >= 1 and ky * kx <= 64
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"View: aa is None, k, (ky, kx) or 'auto' with integers ky, kx >= 1 and "
+                         f"ky kx <= 64, not {aa!r}")
+    return int(ky), int(kx)
+
+
 class View:
     """An output size and window of a frame model of ``src_h`` x ``src_w``:
     ``size=(H2, W2)`` (default: the source's) and ``crop=(x0, y0, w, h)`` in
@@ -262,11 +286,24 @@ class View:
     gsvc_render_frames_resampled).  ValueError for a window outside the frame
     or a non-positive size.  ``out_h``, ``out_w``, ``is_identity``; the four
     tables as numpy arrays (``host_tables``) and, cached per device, as tensors
-    (``device_tables``).  Views point-sample: a downscale aliases where splats
-    are smaller than an output pixel (average an odd-factor upscale to
-    supersample)."""
+    (``device_tables``).
 
-    def __init__(self, src_h: int, src_w: int, size=None, crop=None):
+    Without ``aa`` a view point-samples: a downscale aliases where splats are
+    smaller than an output pixel.  ``aa=(ky, kx)`` (or ``k`` for both, or
+    ``"auto"``: per axis min(8, ceil(window / size))) makes every output pixel
+    the box mean of ky x kx point samples: those of the ``fine`` view,
+    ``View(src_h, src_w, (ky H2, kx W2), crop)``, sample (ky i' + a, kx j' + b)
+    for pixel (i', j'), each evaluated with its own owner tile's list and
+    clamped, summed in float32 in the order include/gsvc_amd.h
+    gsvc_render_frames_filtered states and divided by ky kx.  ``aa`` holds the
+    factors, integers >= 1 with ky kx <= 64; None, 1 and (1, 1) are the
+    point-sampled view (its own ``fine``).  The four tables above stay those of
+    the H2 x W2 point-sampled view; the filtered composite takes
+    ``fine.host_tables()``.  ValueError also where the sub-samples of one output
+    pixel reach past the tile after the first one's along an axis (more than
+    about 16 source pixels per output pixel), decided from the fine tables."""
+
+    def __init__(self, src_h: int, src_w: int, size=None, crop=None, aa=None):
         import numpy as np
         self.src_h, self.src_w = int(src_h), int(src_w)
         if self.src_h < 1 or self.src_w < 1:
@@ -301,6 +338,16 @@ class View:
         self.col_start = np.ascontiguousarray(col_start)
         self.row_start = np.ascontiguousarray(row_start)
         self._device = {}
+        self.aa = _aa_factors(aa, h, self.out_h, w, self.out_w)
+        self.fine = self
+        if self.aa != (1, 1):
+            ky, kx = self.aa
+            self.fine = View(self.src_h, self.src_w, (ky * self.out_h, kx * self.out_w), self.crop)
+            for p, k, axis in ((self.fine.py, ky, "rows"), (self.fine.px, kx, "columns")):
+                t = (p >> 4).reshape(-1, k)
+                if int((t[:, -1] - t[:, 0]).max()) > 1:
+                    raise ValueError(f"View: aa={self.aa} puts the sub-sample {axis} of one output pixel on "
+                                     "more than two source tiles (a pixel may span two per axis)")
 
     def host_tables(self):
         """(sample_x float32 [W2], sample_y float32 [H2], col_start int32
@@ -318,28 +365,29 @@ class View:
 _views = {}
 
 
-def view_of(src_h: int, src_w: int, size=None, crop=None) -> View:
-    """``View(src_h, src_w, size, crop)``, kept for the next call with the
+def view_of(src_h: int, src_w: int, size=None, crop=None, aa=None) -> View:
+    """``View(src_h, src_w, size, crop, aa)``, kept for the next call with the
     same arguments (a decoder asks once per batch)."""
     try:
         key = (int(src_h), int(src_w), None if size is None else tuple(size),
-               None if crop is None else tuple(crop))
+               None if crop is None else tuple(crop), tuple(aa) if isinstance(aa, list) else aa)
         hash(key)
     except TypeError:
-        return View(src_h, src_w, size, crop)  # (its ValueError)
+        return View(src_h, src_w, size, crop, aa)  # (its ValueError)
     v = _views.get(key)
     if v is None:
         if len(_views) >= 64:
             _views.clear()
-        v = _views[key] = View(src_h, src_w, size, crop)
+        v = _views[key] = View(src_h, src_w, size, crop, aa)
     return v
 
 
 def _render_frames_view_cpu(xyz, cholesky, features, sizes, background, xyz_tanh, cholesky_bound,
                             rgb_w, opacity, view: View) -> Tensor:
     """render_frames_sum(view=) for CPU tensors: frame by frame through the
-    CPU statement of the resampled forward (cpu.render_sum_resampled)."""
-    from .cpu import render_sum_resampled
+    CPU statement of the resampled forward (cpu.render_sum_view: the view's
+    fine view, box-reduced where it has ``aa``)."""
+    from .cpu import render_sum_view as render_sum_resampled
     imgs, a = [], 0
     for n in sizes:
         sl = slice(a, a + n)
@@ -373,8 +421,10 @@ def render_frames_sum(xyz: Tensor, cholesky: Tensor, features: Tensor, frame_siz
     window, [F, 3, view.out_h, view.out_w], through
     gsvc_render_frames_resampled -- the same projection and per-tile lists,
     composited at the view's sample positions (an identity view takes that
-    kernel too, and gives the bits of ``view=None``).  With a view, CPU tensors
-    go through the CPU statement of the same forward."""
+    kernel too, and gives the bits of ``view=None``).  A view with ``aa`` goes
+    through gsvc_render_frames_filtered: the box mean of its fine view's
+    samples, reduced inside the composite.  With a view, CPU tensors go through
+    the CPU statement of the same forward."""
     import ctypes
     H, W = int(img_height), int(img_width)
     if view is not None and (view.src_h, view.src_w) != (H, W):
@@ -422,6 +472,29 @@ def render_frames_sum(xyz: Tensor, cholesky: Tensor, features: Tensor, frame_siz
     if bw.offs_host is None or list(bw.offs_host) != offs:
         bw.offs_host = (ctypes.c_int * (F + 1))(*offs)
         bw.offs = torch.tensor(offs, dtype=torch.int32, device=dev)
+    if view is not None and view.aa != (1, 1):
+        # the fine view's tables; the workspace and call parity of the other entries
+        ky, kx = view.aa
+        host = view.fine.host_tables()
+        tabs = view.fine.device_tables(dev)
+        need = 12 * F * view.out_h * view.out_w  # [F, 4 slots, 3, H2, W2]
+        if bw.parts is None or bw.parts.numel() < need:
+            bw.parts = torch.empty((need,), dtype=torch.float32, device=dev)
+        out = torch.empty((F, 3, view.out_h, view.out_w), dtype=torch.float32, device=dev)
+        rc = L.load().gsvc_render_frames_filtered(
+            F, bw.offs_host, bw.offs.data_ptr(), p_xyz, 1 if xyz_tanh else 0, p_chol, p_bound, p_feat,
+            p_rgbw, p_opac, p_bg, H, W, bw.call, bw.hint, bw.meta.data_ptr(), bw.buf.data_ptr(),
+            bw.buf.numel(), host[0].ctypes.data, host[1].ctypes.data, host[2].ctypes.data,
+            host[3].ctypes.data, tabs[0].data_ptr(), tabs[1].data_ptr(), tabs[2].data_ptr(),
+            tabs[3].data_ptr(), ky, kx, view.out_h, view.out_w, bw.parts.data_ptr(),
+            4 * bw.parts.numel(), out.data_ptr(), stream_handle)
+        if rc != 0:
+            bw.key = None
+            msg = L.load().gsvc_last_error().decode(errors="replace")
+            raise RuntimeError(f"gsvc_render_frames_filtered failed (status {rc}): {msg}")
+        bw.call += 1
+        bw.update_hint()
+        return out
     if view is not None:
         # the same workspace and call parity as the native entry: both leave
         # the counts of the other parity zero

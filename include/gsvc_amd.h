@@ -611,7 +611,8 @@ int gsvc_render_frames_sum(int frames, const int *frame_offsets_host,
  * at scale 1 xd = x0 + j' (the native render's window), and an odd integer
  * upscale k puts output column k j + (k - 1) / 2 at x0 + j.  Other views
  * point-sample the trained function: no prefilter, so a downscale aliases
- * where splats are smaller than an output pixel.
+ * where splats are smaller than an output pixel (gsvc_render_frames_filtered
+ * below adds a box prefilter).
  * Projection, workspace, zeroed bytes, call_index parity and meta are those of
  * gsvc_render_frames_sum at the source size img_height x img_width (one
  * workspace may serve both entries); density_hint is accepted and unused.
@@ -630,6 +631,62 @@ int gsvc_render_frames_resampled(int frames, const int *frame_offsets_host,
                                  const float *sample_y_dev, const int *col_start_dev,
                                  const int *row_start_dev, unsigned out_h, unsigned out_w,
                                  float *out, void *stream);
+
+/* The same views with a box prefilter, reduced inside the composite (not part
+ * of the reference): out [frames,3,out_h,out_w], every output pixel the mean
+ * of ky x kx point samples, ky, kx >= 1 and ky kx <= 64.
+ *
+ * The rule.  The FINE view of a view (out_h, out_w, window) is the
+ * point-sampled view of size (ky out_h, kx out_w) over the same window: the
+ * sampling rule above with out_h, out_w replaced, nothing else.  The four
+ * tables given here are the fine view's (sample_x float[kx out_w], col_start
+ * partitioning [0, kx out_w); rows alike).  Output pixel (i', j') is the box
+ * mean of the fine samples (ky i' + a, kx j' + b), 0 <= a < ky, 0 <= b < kx,
+ * each evaluated with the entry list of ITS OWN owner tile and clamped to
+ * [0, 1] as the fine view's image is.  (A pixel is not owned by one tile: a
+ * splat that does not reach the tile of the pixel's centre can still cover a
+ * sub-sample a few source pixels outside it.)  The summation order, float32
+ * throughout, is part of the rule:
+ *   - the pixel's sub-samples are split by owner tile into up to 2 x 2 parts,
+ *         slot = 2 (tile row - tile row of sub-row ky i')
+ *                + (tile column - tile column of sub-column kx j');
+ *   - each part is summed in row-major (a, b) order, starting from +0.0f;
+ *   - the parts are added in slot order;
+ *   - the sum is divided by (float)(ky kx), correctly rounded.
+ * A pixel inside one tile is therefore the plain row-major sum.  ky = kx = 1
+ * is the point-sampled view, bit for bit.
+ * Two tiles per axis: along an axis the tile of a pixel's last sub-sample is
+ * the tile of its first one or the next (so every slot is 0..3; tiles are
+ * counted from the first to the last, a skipped tile included).  A view that
+ * breaks this -- more than about 16 source pixels per output pixel -- is
+ * refused, decided from the start tables, not from the scale.
+ *
+ * parts: float[frames][4 slots][3][out_h][out_w], sized for the full output
+ * (parts_bytes >= 48 frames out_h out_w; small, this is a downscale), scratch
+ * of this call alone: the composite writes the part of every (pixel, slot)
+ * whose pixel straddles a tile edge, a second kernel adds a straddler's parts
+ * in slot order, divides and stores; it reads only slots written by this call,
+ * so the buffer needs no initial value and carries nothing between calls.
+ *
+ * GSVC_ERR_ARG before any launch unless ky kx <= 64, the tables pass the
+ * checks of gsvc_render_frames_resampled for ky out_h x kx out_w, the
+ * two-tiles condition holds and parts is there and large enough.  Everything
+ * else -- projection at the source size, workspace, zeroed bytes, call_index
+ * parity, meta, density_hint -- is gsvc_render_frames_resampled's; one
+ * workspace may serve all three batched entries in any order. */
+int gsvc_render_frames_filtered(int frames, const int *frame_offsets_host,
+                                const int *frame_offsets_dev, const float *xyz, int xyz_tanh,
+                                const float *cholesky, const float *cholesky_bound,
+                                const float *features, const float *rgb_w, const float *opacity,
+                                const float *background, unsigned img_height, unsigned img_width,
+                                int call_index, int density_hint, int *meta, void *workspace,
+                                size_t workspace_bytes, const float *sample_x_host,
+                                const float *sample_y_host, const int *col_start_host,
+                                const int *row_start_host, const float *sample_x_dev,
+                                const float *sample_y_dev, const int *col_start_dev,
+                                const int *row_start_dev, unsigned ky, unsigned kx, unsigned out_h,
+                                unsigned out_w, float *parts, size_t parts_bytes, float *out,
+                                void *stream);
 
 /* Replaces _C.rasterize_sum_backward (bindings.cu:706-779 -> backward.cu:696-862).
  * Gradients are written into one 64-byte record per splat,

@@ -17,12 +17,20 @@ variant in alternating windows (DESIGN.md §13g holds the figures):
     half       960x540
     crop       the centre quarter of the frame (960x540 source pixels) at
                1920x1080
+    quarter    480x270, point-sampled
+    half_aa2   960x540 with ``aa=2``: the filtered composite
+    quarter_aa4  480x270 with ``aa=4``
+    half_2pass, quarter_2pass
+               the two-pass baseline of each ``aa`` variant, what there was
+               before the filtered composite: the fine point-sampled view into
+               a temporary, then ``torch.nn.functional.avg_pool2d``
 
 Every figure is the median of ``--reps`` (at least 5) windows between device
 events, each ``--window`` seconds long, after a warm-up of every shape.  A row
 also gives the composite's lane use from the view's tables -- samples over 64 x
 the 64-sample chunks the tiles walk -- and the share of source tiles that own
-no sample.  ``--trace`` runs ``--trace-calls`` calls of each variant and
+no sample; for an ``aa`` view the lane use of the filtered composite's trips
+and its seam pixels (the output pixels that straddle a tile edge).  ``--trace`` runs ``--trace-calls`` calls of each variant and
 nothing else: the run to put under ``rocprofv3 --kernel-trace``, whose kernel
 table splits a call into projection and composite (``--summarize DIR`` reads
 it back per variant).  Fails without a HIP device."""
@@ -78,10 +86,37 @@ def lane_use(view):
     return float(samples.sum()) / float(64 * chunks.sum()), float((samples == 0).mean())
 
 
+def lane_use_aa(view):
+    """(busy lanes / lanes issued, seam pixels, output pixels) of the filtered
+    composite, from the fine view's tables: a tile touches the output pixels
+    that hold one of its sub-samples and walks them floor(64 / (ky kx)) a trip."""
+    ky, kx = view.aa
+    per_trip = 64 // (ky * kx)
+    rs, cs = view.fine.row_start.astype(np.int64), view.fine.col_start.astype(np.int64)
+    own_r, own_c = (rs[1:] > rs[:-1]), (cs[1:] > cs[:-1])
+    pr = np.where(own_r, (rs[1:] - 1) // ky + 1 - rs[:-1] // ky, 0)[:, None]
+    pc = np.where(own_c, (cs[1:] - 1) // kx + 1 - cs[:-1] // kx, 0)[None, :]
+    trips = (pr * pc + per_trip - 1) // per_trip
+    seam_r = int(((rs[1:-1] % ky) != 0).sum())  # a tile range that starts inside a pixel
+    seam_c = int(((cs[1:-1] % kx) != 0).sum())
+    seam = seam_r * view.out_w + seam_c * view.out_h - seam_r * seam_c
+    samples = float(view.fine.out_h) * float(view.fine.out_w)
+    return samples / float(64 * trips.sum()), seam, view.out_h * view.out_w
+
+
+VARIANTS = ["native", "identity", "up2", "half", "crop", "quarter", "half_aa2", "half_2pass", "quarter_aa4",
+            "quarter_2pass"]
+_CLASSES = (("projection_us", ("frame_project_kernel",)),
+            ("composite_us", ("raster_resampled_kernel", "raster_sum_fwd_kernel", "raster_filtered_kernel")),
+            ("seams_us", ("filter_seams_kernel",)), ("pool_us", ("avg_pool", "AvgPool")))
+
+
 def summarize(trace_dir, calls):
     """The kernel table of a ``--trace`` run under rocprofv3 (csv): per variant,
-    in the order it ran, the median microseconds of the projection and of the
-    composite over its last ``calls`` calls."""
+    in the order it ran, the median microseconds per call of the projection,
+    the composite, the filtered composite's seam kernel and the two-pass
+    baseline's pooling kernel over its last ``calls`` calls.  A call begins at
+    its projection kernel."""
     import csv
     import glob
     rows = []
@@ -90,15 +125,22 @@ def summarize(trace_dir, calls):
             rows += [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"])
                      for r in csv.DictReader(fh)]
     rows.sort()
-    comp = [(e - s) / 1e3 for s, e, k in rows if "raster_resampled_kernel" in k or "raster_sum_fwd_kernel" in k]
-    proj = [(e - s) / 1e3 for s, e, k in rows if "frame_project_kernel" in k]
-    names = ["native", "identity", "up2", "half", "crop"]
-    per = len(comp) // len(names)
+    per_call = []
+    for s, e, k in rows:
+        if "frame_project_kernel" in k:
+            per_call.append({})
+        if not per_call:
+            continue
+        for key, words in _CLASSES:
+            if any(w in k for w in words):
+                per_call[-1][key] = per_call[-1].get(key, 0.0) + (e - s) / 1e3
+    per = len(per_call) // len(VARIANTS)
     out = {}
-    for i, name in enumerate(names):
-        c, p = comp[i * per:(i + 1) * per][-calls:], proj[i * per:(i + 1) * per][-calls:]
-        out[name] = {"composite_us": round(statistics.median(c), 2), "projection_us": round(statistics.median(p), 2),
-                     "calls": len(c)}
+    for i, name in enumerate(VARIANTS):
+        mine = per_call[i * per:(i + 1) * per][-calls:]
+        out[name] = {key: round(statistics.median(c.get(key, 0.0) for c in mine), 2) for key, _ in _CLASSES
+                     if any(key in c for c in mine)}
+        out[name]["calls"] = len(mine)
     print(json.dumps(out), flush=True)
     return out
 
@@ -134,29 +176,57 @@ def main(argv=None):
     sizes = [n] * F
     views = {"native": None, "identity": View(H, W), "up2": View(H, W, size=(2 * H, 2 * W)),
              "half": View(H, W, size=(H // 2, W // 2)),
-             "crop": View(H, W, size=(H, W), crop=(W // 4, H // 4, W // 2, H // 2))}
+             "crop": View(H, W, size=(H, W), crop=(W // 4, H // 4, W // 2, H // 2)),
+             "quarter": View(H, W, size=(H // 4, W // 4)),
+             "half_aa2": View(H, W, size=(H // 2, W // 2), aa=2),
+             "half_2pass": View(H, W, size=(H // 2, W // 2), aa=2),
+             "quarter_aa4": View(H, W, size=(H // 4, W // 4), aa=4),
+             "quarter_2pass": View(H, W, size=(H // 4, W // 4), aa=4)}
+    assert list(views) == VARIANTS
 
-    def call(view):
-        return lambda: render_frames_sum(xyz, chol, feat, sizes, H, W, bg, cholesky_bound=bound, view=view)
+    def render(view):
+        return render_frames_sum(xyz, chol, feat, sizes, H, W, bg, cholesky_bound=bound, view=view)
+
+    def call(view, two_pass=False):
+        if two_pass:  # the fine view into a temporary, then the box mean by torch
+            return lambda: torch.nn.functional.avg_pool2d(render(view.fine), view.aa)
+        return lambda: render(view)
+
+    calls = {name: call(view, name.endswith("_2pass")) for name, view in views.items()}
 
     with torch.no_grad():
         if args.trace:
-            for name, view in views.items():
+            for name in views:
                 for _ in range(args.trace_calls):
-                    call(view)()
+                    calls[name]()
                 torch.cuda.synchronize()
             print(json.dumps({"trace_calls": args.trace_calls, "order": list(views)}), flush=True)
             return None
         same = bool(torch.equal(call(None)(), call(views["identity"])()))
+        # float32 pooling sums in another order than the rule: close, not equal
+        aa_err = {name: float((calls[name]() - calls[name.replace("_aa2", "_2pass").replace("_aa4", "_2pass")]())
+                              .abs().max()) for name in ("half_aa2", "quarter_aa4")}
         from gsvc_amd import render as R
         bw = next(iter(R._batch_workspaces.values()))
         m = int(bw.meta[:, 0].sum())
         line = {"device": torch.cuda.get_device_name(0), "H": H, "W": W, "frames": F, "splats": n,
                 "chol_scale": args.chol_scale, "entries_per_tile": round(m / (F * 68 * 120), 2),
-                "identity_equals_native": same, "reps": args.reps, "window_s": args.window}
-        res = compare({name: call(view) for name, view in views.items()}, args.reps, args.window)
+                "identity_equals_native": same, "max_abs_fused_minus_two_pass": aa_err, "reps": args.reps,
+                "window_s": args.window}
+        res = compare(calls, args.reps, args.window)
         for name, view in views.items():
-            if view is not None:
+            if name.endswith("_2pass"):  # the composite of the fine view, point-sampled
+                use, empty = lane_use(view.fine)
+                res[name].update(out=[view.out_h, view.out_w], aa=list(view.aa), lane_use=round(use, 4),
+                                 temporary_bytes=4 * F * 3 * view.fine.out_h * view.fine.out_w)
+                fused = res[name.replace("half_2pass", "half_aa2").replace("quarter_2pass", "quarter_aa4")]
+                fused["vs_two_pass"] = round(fused["median_us"] / res[name]["median_us"], 3)
+                fused["inside_two_pass_range"] = bool(fused["median_us"] <= res[name]["max_us"])
+            elif view is not None and view.aa != (1, 1):
+                use, seam, pixels = lane_use_aa(view)
+                res[name].update(out=[view.out_h, view.out_w], aa=list(view.aa), lane_use=round(use, 4),
+                                 seam_pixels=seam, seam_share=round(seam / pixels, 4))
+            elif view is not None:
                 use, empty = lane_use(view)
                 res[name].update(out=[view.out_h, view.out_w], lane_use=round(use, 4),
                                  tiles_without_samples=round(empty, 4))
