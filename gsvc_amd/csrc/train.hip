@@ -451,15 +451,15 @@ __global__ __launch_bounds__(256, 8) void train_tile_kernel(TrainTileArgs A) {
 //      entry order, with the render's op sequence at unit opacity (1 * e ==
 //      e: the same image bits); clamp, loss gradient, error sums; v_out planes
 //      into LDS.
-//   3. backward, each wave over the rectangle rows of its own band: work
-//      items = one row of an entry's rectangle (the row terms of sigma
-//      shared; per-pixel sums factored by dy), entries laid out longest rows
-//      first in four length classes, rounds of 64 items; per round a DPP
-//      segmented scan (one v_fmac_f32_dpp per sum and step) gives each run of
-//      an entry's items its sum, which the run's last item adds to the
-//      entry's LDS sums (a fixed order, no LDS atomics); then 8 lanes per
-//      entry add the two bands' 32 bytes into the splat's gradient record
-//      (one request per (splat, tile)).
+//   3. backward over the rectangle rows of the whole tile: work items = one
+//      row of an entry's rectangle (the row terms of sigma shared; per-pixel
+//      sums factored by dy), entries laid out longest rows first in eight
+//      length classes, rounds of 64 items dealt to the two waves; per round a
+//      DPP segmented scan (one v_fmac_f32_dpp per sum and step) gives each
+//      run of an entry's items its sum, which the run's last item adds to the
+//      entry's LDS sums of its wave (a fixed order, no LDS atomics); then 8
+//      lanes per entry add the two waves' 32 bytes into the splat's gradient
+//      record (one request per (splat, tile)).
 // GSVC's opacity is ones (GaussianSplats_Represent.py:84) and the training
 // step projects with opacity 1, so the opacity gradient (record slot 8) is
 // not formed.
@@ -1234,8 +1234,13 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
 
     if (kDiag && (A.diag & 2)) return;  // diagnostic: no backward (wrong results)
     // 4. backward, kBChunk entries at a time (sparse tiles: the forward's staging).
-    // Each wave takes the rectangle rows of its own band -- the v_out rows it
-    // wrote itself -- so the waves need no barrier until the chunk's flush.
+    // The items of both bands are one table per tile and chunk, which each wave
+    // builds for itself (the same table in both); its rounds of 64 items are
+    // dealt to the two waves (the round loop's step).  A wave therefore reads v_out
+    // rows the other wave wrote: the barrier after the planes' stores (the one
+    // before the tile's error sums are added) orders them.  Between that
+    // barrier and the chunk's flush the waves share nothing else: each has its
+    // own entry sums, slot scatter and permutation.
     float *eacc = &S.part[0][0] + w * (8 * kBChunk);  // [8][kBChunk] entry sums per wave
     signed char *wown = S.own + w * 64;
     signed char *wperm = S.perm + w * 64;
@@ -1250,19 +1255,18 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
             stage_chunk(S.gid, gn);
             __syncthreads();
         }
-        // work items of entry `lane` in this band: one per rectangle row, two
-        // halves when the row is wider than brun
+        // work items of entry `lane` in the tile: one per rectangle row (rows
+        // below the image too: items without pixel work), two halves when the
+        // row is wider than brun
         int items = 0, ilen = 0;
         unsigned rc = kNoRect;
         if (lane < gn) {
             rc = S.ro[lane];
-            if (rc != kNoRect) {
-                const int ry0 = max((int)((rc >> 8) & 15u), y_lo), ry1 = min((int)((rc >> 12) & 15u), y_hi);
+            if (rc != kNoRect) {  // (a rectangle has y0 <= y1)
+                const int ry0 = (int)((rc >> 8) & 15u), ry1 = (int)((rc >> 12) & 15u);
                 const int rw = (int)((rc >> 4) & 15u) - (int)(rc & 15u) + 1;
-                if (ry0 <= ry1) {
-                    items = (ry1 - ry0 + 1) * (rw > kBRun ? 2 : 1);
-                    ilen = rw > kBRun ? (rw + 1) >> 1 : rw;
-                }
+                items = (ry1 - ry0 + 1) * (rw > kBRun ? 2 : 1);
+                ilen = rw > kBRun ? (rw + 1) >> 1 : rw;
             }
         }
         // the entries' items are laid out longest first (by class, stable), so a
@@ -1272,17 +1276,17 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         {
             int rank = 0, seen = 0;
             unsigned long long left = __ballot(true);
-            // four length classes (9+, 7-8, 5-6, <= 4), entry order within a
-            // class: most of an exact sort's gain for a quarter of its VALU.
-            // Entries without items in this band (and the lanes past the
-            // chunk) are a fifth class, ranked last -- what the four leave
-            // over, no compare of its own: the slots that carry items are a
-            // prefix of the sorted order, which the rounds' item -> slot
-            // count relies on.  The items' layout is what it was: those
-            // entries held none.
-            int cls = ilen >= 9 ? 4 : (ilen >= 7 ? 3 : (ilen >= 5 ? 2 : (items > 0 ? 1 : 0)));
+            // eight length classes (15-16, 13-14, ..., 1-2), entry order within
+            // a class: with the tile's ~224 items pooled a round spans a
+            // quarter of the lengths, and eight classes get within 2 % of an
+            // exact sort's trips (tests/analysis/pool_sim.py; four: 10 % off).
+            // Entries without items (and the lanes past the chunk) are a
+            // ninth class, ranked last -- what the eight leave over, no
+            // compare of its own: the slots that carry items are a prefix of
+            // the sorted order, which the rounds' item -> slot count relies on.
+            int cls = items > 0 ? ((ilen - 1) >> 1) + 1 : 0;
             if (kDiag && (A.diag & 64)) cls = items > 0 ? 1 : 0;  // A/B: entry order (no items: last)
-            for (int L = 4; L >= 1 && left; --L) {
+            for (int L = 8; L >= 1 && left; --L) {
                 const unsigned long long m = __ballot(cls == L);
                 if (cls == L) rank = seen + lanes_below(m);
                 seen += (int)__popcll(m);
@@ -1313,7 +1317,12 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         // different registers and moved them back every round (ISA: 83
         // v_mov_b32 of 337 VALU per round).  Same sums bit for bit.
         auto rounds = [&](auto kcut) {
-            for (int base = 0; base < total; base += 64) {
+            // the rounds are dealt as a snake, 0 1 1 0 0 1 1 0 ...: they come
+            // longest first, so alternating would give wave 0 the longer of
+            // every pair (pool_sim.py: 193 k against 127 k trips a launch;
+            // the snake 156 k / 165 k).  From round r of a wave its next is
+            // r + 3 (r even) or r + 1 (r odd), for either wave.
+            for (int base = 64 * w; base < total; base += (base & 64) ? 64 : 192) {
                 // the sorted slot of item base + lane: the last slot whose first
                 // item is <= it.  The slots with items are the sorted order's
                 // prefix, first items ascending (the others, and the lanes past
@@ -1342,7 +1351,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                 const int rwid = rx1 - rx0 + 1;
                 const int ipr = rwid > kBRun ? 2 : 1;
                 const int jr = ipr == 1 ? j : (j >> 1);
-                const int row = max((int)((ro >> 8) & 15u), y_lo) + jr;
+                const int row = (int)((ro >> 8) & 15u) + jr;
                 const int half = (rwid + 1) >> 1;
                 const int cs = ipr == 1 ? rx0 : rx0 + half * (j & 1);
                 const int ce = min(ipr == 1 ? rx1 : min(cs + half - 1, rx1), A.img_w - 1 - (int)tx0);
@@ -1458,11 +1467,13 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
                 // alternatives: every item adding its sums with LDS float atomics
                 // (2.9x slower kernel: the LDS serialises an entry's items); a
                 // packed two-pixel loop (80 VGPRs, 6 waves per SIMD: 64.0 vs 58.5
-                // us).  An entry has at most 8 items in a band unless rows split
-                // in two (kBRun < 16): runs of <= 8 lanes need no row_shr:8 step (a
-                // run crossing a 16-lane row still takes the row broadcast)
+                // us).  An entry has up to 16 items in the tile (32 when rows
+                // split in two, kBRun < 16), so a run can fill a 16-lane row:
+                // the scan's row_shr:8 step is in (kLong).  A run cut by a
+                // round boundary ends in two rounds, of one wave or of both:
+                // either way each piece's sum goes to its wave's entry sums.
                 if (!(kDiag && (A.diag & 16)))  // diag 16: no run sums (wrong)
-                    wave_seg_sums<8, (kBRun < 16)>(g, own);
+                    wave_seg_sums<8, true>(g, own);
                 const int own_next = __shfl_down(own, 1, 64);
                 if (item < total && (lane == 63 || item + 1 == total || own_next != own)) {
 #pragma unroll
@@ -1476,7 +1487,7 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         else
             rounds(std::false_type{});
         __syncthreads();
-        // 8 lanes per entry add the entry's sums (band 0 + band 1) into the
+        // 8 lanes per entry add the entry's sums (wave 0's + wave 1's) into the
         // splat's gradient record
         if (kDet) {
             // deterministic: one 32-byte partial per (splat, tile) at the tile's
