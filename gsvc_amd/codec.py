@@ -6,8 +6,7 @@ video's frame streams into ONE file with an index (``write_video`` /
 (8-bit I420 by default; 8 to 16 bits, BT.601 or BT.709, limited or full range,
 4:2:0 / 4:2:2 / 4:4:4, planar or semi-planar as NV12 / P010:
 ``video.YuvFormat``) in batches on the GPU (``decode_video``:
-``decode_frames(output="i420")``, csrc/yuv_out.hip, csrc/yuv_fmt.hip and
-csrc/yuv_layout.hip), and is the command line of the three steps:
+``decode_frames(output="i420")``, csrc/yuv_conv.hip), and is the command line of the three steps:
 
     python -m gsvc_amd.codec encode MODELS.pth SRC.yuv OUT.gsvf --width W --height H
     python -m gsvc_amd.codec info OUT.gsvf

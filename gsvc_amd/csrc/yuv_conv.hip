@@ -1,38 +1,66 @@
-// YUV in and out beyond planar 4:2:0 (gfx950): 4:2:2 and 4:4:4 planar, and
-// semi-planar 4:2:0 / 4:2:2 / 4:4:4 (plane Y, then one plane of interleaved U, V
-// pairs, U first: NV12 / NV16 / NV24 and the P010 / P210 / P410 families), for
-// every colour triple of gsvc_yuv_format, a whole batch per launch.  Not part
-// of the reference.  Planar 4:2:0 stays with yuv.hip / yuv_out.hip / yuv_fmt.hip
-// and is refused here.
+// The batch YUV conversions, both directions (gfx950): float RGB planes
+// [F, 3, H, W] <-> frames of YUV samples, a whole batch per launch, for every
+// colour triple of gsvc_yuv_format (8, 10, 12 or 16 bits; BT.601 or BT.709;
+// limited or full range) in six layouts: 4:2:0, 4:2:2 and 4:4:4, each planar
+// (planes Y, U, V) or semi-planar (plane Y, then one plane of interleaved U, V
+// pairs, U first: NV12 / NV16 / NV24 and the P010 / P210 / P410 families).  Not
+// part of the reference, which writes no YUV and reads 8-bit I420 only; that one
+// restatement (gsvc_i420_to_rgb, one frame, OpenCV's path) stays in yuv.hip.
+//
+// One kernel family serves five C entries (DESIGN.md §13d-f tell how three
+// generations of it came to be, §13i how they were merged):
+//   gsvc_rgb_to_i420                        8-bit planar 4:2:0 out, legacy constants;
+//   gsvc_yuv420_to_rgb / gsvc_rgb_to_yuv420 planar 4:2:0 of every other triple;
+//   gsvc_yuv_to_rgb / gsvc_rgb_to_yuv       the five other layouts, every triple.
+// Each entry refuses what belongs to another (conversion_args), so a format has
+// one definition; gsvc_yuv_format_table (host only) is here too.
 //
 // Arithmetic (include/gsvc_amd.h; integer after the quantizer, so both
-// directions are bit-exact against tests/yuv_layout_cases.py): yuv_fmt.hip's
-// formulas with the chroma block generalised: a chroma sample serves 2x2, 2x1
-// or 1 pixels, and the output shift is 20 + log2 of that count.  The
-// coefficients are gsvc_yuv_format_table's, but for the legacy triple (8-bit
-// bt601 limited range) the legacy kernels' constants: one definition per colour
-// triple, so nv12 is a byte permutation of gsvc_rgb_to_i420's I420.  Products
-// are widened to 64 bits above 8 bits per sample and stay int32 at 8 bits
-// (tests/test_yuv_layouts_cpu.py re-derives the bounds per layout).
+// directions are bit-exact against tests/yuv_cases.py, yuv_format_cases.py and
+// yuv_layout_cases.py): every channel is clamped to [0, 1] (NaN -> 0), scaled by
+// the peak, 0.5 added and truncated; luma at 20 bits per pixel; chroma from the
+// SUM of the quantized pixels its sample serves (2x2, 2x1 or 1), shifted by 20 +
+// log2 of that count, one rounding.  The coefficients are
+// gsvc_yuv_format_table's exact 20-bit ones, evaluated in double on the host,
+// but for the legacy triple (8-bit bt601 limited range) OpenCV's three-decimal
+// constants (kLegacyTable, as yuv.hip): one definition per colour triple, so
+// nv12 is a byte permutation of gsvc_rgb_to_i420's I420.  Every coefficient and
+// every sample fits an int; products are widened to 64 bits above 8 bits per
+// sample (65535 * 1.2 * 2^20 passes 2^36) and stay int32 at 8 bits (below 1.1e9
+// in both directions; tests/test_yuv_out_cpu.py, test_yuv_formats_cpu.py and
+// test_yuv_layouts_cpu.py re-derive the bounds).
 //
 // Semi-planar words above 8 bits carry the value in the high bits (P010: word =
 // value << (16 - b)); the shift is applied after loading (low bits ignored) and
 // before packing (low bits zero).
 //
-// Two layouts of the work, same bytes.  Vector (W % 8 == 0, every buffer
-// 16-byte aligned): one lane per R rows x 8 columns (R = 2 at 4:2:0, else 1),
-// every load issued before first use; Y moves as 8 samples per row, planar
+// Two layouts of the work, same bytes.  Vector (W % 8 == 0 and the buffers
+// aligned, vector_path): one lane per R rows x 8 columns (R = 2 at 4:2:0, else
+// 1), every load issued before first use; Y moves as 8 samples per row, planar
 // chroma as 4 U + 4 V samples (8 + 8 at 4:4:4), interleaved chroma as 8 samples
 // per access (two at 4:4:4): 8 samples are 16 bytes at 16 bits and 8 bytes at
 // 8 bits, and every such access is aligned to its own width (DESIGN.md §13f
-// goes through the five layouts).  Fallback (everything else, odd sizes
-// included): one lane per chroma block, sample-wide accesses.  grid (blocks of
-// one frame, frames), no stride loop: a block lies inside one frame.
+// goes through the layouts).  The float planes must be 16-byte aligned; the
+// sample buffers 16-byte too, except in gsvc_rgb_to_i420, whose 8-bit planar
+// 4:2:0 accesses are 8 and 4 bytes wide and which has always asked for 8 (an
+// 18x24 frame is 648 bytes, so every second frame of a batch starts 8 mod 16).
+// Fallback (everything else, odd sizes included; at 4:2:0 with H*W/4 odd the V
+// plane and every second frame start at odd or 2-mod-4 offsets): one lane per
+// chroma block, sample-wide accesses.  HBM-bound: 12 B read + 1.5 samples
+// written per 4:2:0 pixel (+1.5 read with ref).
+//
+// grid (blocks of one frame, frames), no stride loop: a block lies inside one
+// frame.  A frame of more than 2^31 - 1 blocks of 256 chroma blocks is refused
+// ("more than one grid of blocks"); gsvc_rgb_to_i420, which used to stride over
+// 4096 blocks per frame, inherits that refusal: it needs 2^31 * 256 chroma
+// blocks in one frame, which no allocation can hold.
 //
 // With ref, squared sample differences (one is < 2^32 at 16 bits) are summed in
 // 64 bits per lane, then by wave, then by block; one 64-bit atomic add per
 // plane and block: exact and run-to-run identical.  Blocks are 256 lanes, but
 // 1024 in the vector instances with ref whose lanes hold one row (out_block).
+#include <math.h>
+
 #include "common.h"
 
 namespace gsvc {
@@ -48,6 +76,18 @@ struct FmtDev {
     int yr, yg, yb, ur, ug, ub, vr, vg, vb;
     int msb;  // semi-planar words above 8 bits: value << msb
 };
+
+// gsvc_yuv_format_table's 18 integers as the kernels take them
+constexpr FmtDev fmt_dev(const long long o[18], int msb) {
+    return FmtDev{(int)o[0], (int)o[1], (int)o[2], (int)o[4], (int)o[5], (int)o[6], (int)o[7], (int)o[8],
+                  (int)o[9], (int)o[10], (int)o[11], (int)o[12], (int)o[13], (int)o[14], (int)o[15],
+                  (int)o[16], (int)o[17], msb};
+}
+
+// the legacy triple's constants (OpenCV's three decimals, as yuv.hip), in the
+// table's order: what every layout computes with at 8-bit bt601 limited range
+constexpr long long kLegacyTable[18] = {255, 16, 128, 1, 1220542, 1673527, -409993, -852492, 2116026,
+                                        269484, 528482, 102760, -155188, -305135, 460324, 460324, -385875, -74448};
 
 template <int kBytes>
 struct Sample {
@@ -73,8 +113,12 @@ __device__ __forceinline__ int hi16(unsigned w) { return (int)(w >> 16); }
 __device__ __forceinline__ int byte_at(unsigned w, int k) { return (int)((w >> (8 * k)) & 255u); }
 
 // Values in [0, 65535] as little-endian words.  The empty asm keeps the clamped
-// values opaque to the compiler's pack-and-saturate folds (yuv_out.hip pack4,
-// DESIGN.md §13d).
+// values opaque: left to itself hipcc folds shift, clamp and the first two
+// bytes' packing into gfx950's v_ashr_pk_u8_i32 and ORs bytes 2 and 3 into its
+// result as if the upper half of that result were zero; on the MI355X the words
+// then came back with bytes 2 and 3 wrong (tests/test_yuv_out_gpu.py caught it,
+// DESIGN.md §13d).  pack2 is kept opaque in the same way against the 16-bit
+// pack-and-saturate folds.
 __device__ __forceinline__ unsigned pack4(int a, int b, int c, int d) {
     asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
     return (unsigned)a | (unsigned)b << 8 | (unsigned)c << 16 | (unsigned)d << 24;
@@ -279,10 +323,18 @@ constexpr int out_block() {
     return (kRef && kVec && Block<kChroma>::rows == 1) ? 1024 : 256;
 }
 
-template <int kBytes, int kChroma, bool kSemi, bool kVec, bool kRef>
-__global__ __launch_bounds__((out_block<kChroma, kVec, kRef>())) void rgb_to_yuv_kernel(const float *__restrict__ rgb, int h, int w, FmtDev t,
-                                                         void *__restrict__ out, const void *__restrict__ ref,
-                                                         unsigned long long *__restrict__ sse, int frame0) {
+// kLegacyImm (gsvc_rgb_to_i420's instances): the legacy triple's constants as
+// immediates instead of the argument's.  Its instance without ref also asks for
+// the registers of 7 waves per SIMD, which yuv_out.hip's kernel had and which
+// the vector layout otherwise misses by three VGPRs (75); the one with ref has
+// them unasked (72) and measures the same either way.
+template <int kBytes, int kChroma, bool kSemi, bool kVec, bool kRef, bool kLegacyImm>
+__global__ __launch_bounds__((out_block<kChroma, kVec, kRef>()))
+__attribute__((amdgpu_waves_per_eu(kLegacyImm && !kRef ? 7 : 1)))
+void rgb_to_yuv_kernel(const float *__restrict__ rgb, int h, int w, FmtDev targ, void *__restrict__ out,
+                       const void *__restrict__ ref, unsigned long long *__restrict__ sse, int frame0) {
+    constexpr FmtDev kImm = fmt_dev(kLegacyTable, 0);
+    const FmtDev t = kLegacyImm ? kImm : targ;
     using S = typename Sample<kBytes>::type;
     using A = typename Sample<kBytes>::acc;
     using U = Unit<kChroma, kSemi, kVec>;
@@ -437,27 +489,77 @@ __global__ __launch_bounds__((out_block<kChroma, kVec, kRef>())) void rgb_to_yuv
 // ---------------------------------------------------------------------------
 // host
 
-// the legacy kernels' constants (yuv.hip, yuv_out.hip), in the table's order
-const long long kLegacyTable[18] = {255, 16, 128, 1, 1220542, 1673527, -409993, -852492, 2116026,
-                                    269484, 528482, 102760, -155188, -305135, 460324, 460324, -385875, -74448};
+double fix20(double x) { return floor(x * 1048576.0 + 0.5); }
 
-// the checks both conversions share; 0 and *t filled, or a status
-int conversion_args(const char *what, int frames, int h, int w, const gsvc_yuv_format *fmt, int chroma,
-                    int semi, const void *a, const void *b, const void *ref, const void *sse,
+// nullptr when the format is one of the 16; else what is wrong with it
+const char *table_of(const gsvc_yuv_format *fmt, long long o[18]) {
+    if (!fmt) return "missing format";
+    const int b = fmt->bit_depth;
+    if (b != 8 && b != 10 && b != 12 && b != 16) return "bit_depth must be 8, 10, 12 or 16";
+    if (fmt->matrix != 0 && fmt->matrix != 1) return "matrix must be 0 (bt601) or 1 (bt709)";
+    if (fmt->full_range != 0 && fmt->full_range != 1) return "full_range must be 0 or 1";
+    const double kr = fmt->matrix ? 0.2126 : 0.299, kb = fmt->matrix ? 0.0722 : 0.114, kg = 1.0 - kr - kb;
+    const long long peak = (1ll << b) - 1;
+    const double p = (double)peak;
+    const double yspan = fmt->full_range ? p : (double)(219ll << (b - 8));
+    const double cspan = fmt->full_range ? p : (double)(224ll << (b - 8));
+    o[0] = peak;
+    o[1] = fmt->full_range ? 0 : (16ll << (b - 8));
+    o[2] = 1ll << (b - 1);
+    o[3] = b == 8 ? 1 : 2;
+    o[4] = (long long)fix20(p / yspan);
+    o[5] = (long long)fix20(2.0 * (1.0 - kr) * p / cspan);
+    o[6] = (long long)fix20(-2.0 * kb * (1.0 - kb) / kg * p / cspan);
+    o[7] = (long long)fix20(-2.0 * kr * (1.0 - kr) / kg * p / cspan);
+    o[8] = (long long)fix20(2.0 * (1.0 - kb) * p / cspan);
+    o[9] = (long long)fix20(kr * yspan / p);
+    o[10] = (long long)fix20(kg * yspan / p);
+    o[11] = (long long)fix20(kb * yspan / p);
+    o[12] = (long long)fix20(-kr / (2.0 * (1.0 - kb)) * cspan / p);
+    o[13] = (long long)fix20(-kg / (2.0 * (1.0 - kb)) * cspan / p);
+    o[14] = (long long)fix20(cspan / (2.0 * p));
+    o[15] = (long long)fix20(cspan / (2.0 * p));
+    o[16] = (long long)fix20(-kg / (2.0 * (1.0 - kr)) * cspan / p);
+    o[17] = (long long)fix20(-kb / (2.0 * (1.0 - kr)) * cspan / p);
+    return nullptr;
+}
+
+const gsvc_yuv_format kLegacyFormat = {8, 0, 0};
+
+// What an entry serves; the rest it refuses, so every format has one entry.
+enum Serves {
+    kLegacyI420,  // gsvc_rgb_to_i420: the legacy triple, planar 4:2:0
+    kPlanar420,   // gsvc_yuv420_to_rgb / gsvc_rgb_to_yuv420: planar 4:2:0 but the legacy triple
+    kLayouts      // gsvc_yuv_to_rgb / gsvc_rgb_to_yuv: every layout but planar 4:2:0
+};
+
+// The checks every conversion entry shares, under the entry's name; 0 and *t
+// filled, or a status.  a, b: the two buffers that must be there; samples, ref:
+// the ones that hold samples.
+int conversion_args(const char *what, Serves serves, int frames, int h, int w, const gsvc_yuv_format *fmt,
+                    int chroma, int semi, const void *a, const void *b, const void *ref, const void *sse,
                     const void *samples, FmtDev *t) {
     if (chroma != 420 && chroma != 422 && chroma != 444)
         return set_error(GSVC_ERR_ARG, "%s: chroma must be 420, 422 or 444, not %d", what, chroma);
     if (semi != 0 && semi != 1) return set_error(GSVC_ERR_ARG, "%s: semi_planar must be 0 or 1", what);
     long long o[18];
-    if (gsvc_yuv_format_table(fmt, o) != GSVC_OK) return GSVC_ERR_ARG;  // the table's message stands
-    if (chroma == 420 && !semi)
+    if (const char *bad = table_of(fmt, o))  // the layouts' entries have always named the table here
+        return set_error(GSVC_ERR_ARG, "%s: %s", serves == kLayouts ? "yuv_format_table" : what, bad);
+    const bool legacy = fmt->bit_depth == 8 && fmt->matrix == 0 && fmt->full_range == 0;
+    if (serves == kLayouts && chroma == 420 && !semi)
         return set_error(GSVC_ERR_ARG, "%s: planar 4:2:0 belongs to gsvc_i420_to_rgb / gsvc_rgb_to_i420 and "
                          "gsvc_yuv420_to_rgb / gsvc_rgb_to_yuv420", what);
+    if (serves == kPlanar420 && legacy)
+        return set_error(GSVC_ERR_ARG, "%s: 8-bit bt601 limited range is the legacy format of "
+                         "gsvc_i420_to_rgb / gsvc_rgb_to_i420", what);
     if (frames <= 0) return set_error(GSVC_ERR_ARG, "%s: frames = %d, must be positive", what, frames);
-    if (h <= 0 || w <= 0) return set_error(GSVC_ERR_ARG, "%s: height and width must be positive", what);
-    if (chroma == 420 && ((h & 1) || (w & 1)))
-        return set_error(GSVC_ERR_ARG, "%s: 4:2:0 needs an even height and width", what);
-    if (chroma == 422 && (w & 1)) return set_error(GSVC_ERR_ARG, "%s: 4:2:2 needs an even width", what);
+    if (serves == kLayouts) {
+        if (h <= 0 || w <= 0) return set_error(GSVC_ERR_ARG, "%s: height and width must be positive", what);
+        if (chroma == 420 && ((h & 1) || (w & 1)))
+            return set_error(GSVC_ERR_ARG, "%s: 4:2:0 needs an even height and width", what);
+        if (chroma == 422 && (w & 1)) return set_error(GSVC_ERR_ARG, "%s: 4:2:2 needs an even width", what);
+    } else if (h <= 0 || w <= 0 || (h & 1) || (w & 1))
+        return set_error(GSVC_ERR_ARG, "%s: height and width must be positive and even", what);
     if (!a || !b) return set_error(GSVC_ERR_ARG, "%s: missing buffer", what);
     if (ref && !sse) return set_error(GSVC_ERR_ARG, "%s: ref needs sse", what);
     if (o[3] == 2 && (((uintptr_t)samples | (uintptr_t)ref) & 1u))
@@ -466,11 +568,9 @@ int conversion_args(const char *what, int frames, int h, int w, const gsvc_yuv_f
     const long long blocks = (long long)(chroma == 420 ? h / 2 : h) * (chroma == 444 ? w : w / 2);
     if ((blocks + 255) / 256 > 2147483647ll)
         return set_error(GSVC_ERR_ARG, "%s: %dx%d is more than one grid of blocks", what, h, w);
-    if (fmt->bit_depth == 8 && fmt->matrix == 0 && fmt->full_range == 0)
+    if (legacy)
         for (int k = 0; k < 18; ++k) o[k] = kLegacyTable[k];
-    *t = FmtDev{(int)o[0], (int)o[1], (int)o[2], (int)o[4], (int)o[5], (int)o[6], (int)o[7], (int)o[8],
-                (int)o[9], (int)o[10], (int)o[11], (int)o[12], (int)o[13], (int)o[14], (int)o[15],
-                (int)o[16], (int)o[17], (semi && fmt->bit_depth > 8) ? 16 - fmt->bit_depth : 0};
+    *t = fmt_dev(o, (semi && fmt->bit_depth > 8) ? 16 - fmt->bit_depth : 0);
     return GSVC_OK;
 }
 
@@ -496,7 +596,7 @@ void launch_in(bool vec, int frames, const void *yuv, int h, int w, const FmtDev
     }
 }
 
-template <int kBytes, int kChroma, bool kSemi, bool kVec>
+template <int kBytes, int kChroma, bool kSemi, bool kVec, bool kLegacyImm>
 void launch_out(int frames, const float *rgb, int h, int w, const FmtDev &t, void *out, const void *ref,
                 unsigned long long *sse, hipStream_t s) {
     for (int f0 = 0; f0 < frames; f0 += kMaxGridY) {
@@ -505,10 +605,10 @@ void launch_out(int frames, const float *rgb, int h, int w, const FmtDev &t, voi
         if (ref) {
             constexpr int kBlock = out_block<kChroma, kVec, true>();
             const dim3 rgrid = grid_of<kChroma, kVec, kBlock>(h, w, fy);
-            hipLaunchKernelGGL((rgb_to_yuv_kernel<kBytes, kChroma, kSemi, kVec, true>), rgrid, dim3(kBlock), 0, s,
+            hipLaunchKernelGGL((rgb_to_yuv_kernel<kBytes, kChroma, kSemi, kVec, true, kLegacyImm>), rgrid, dim3(kBlock), 0, s,
                                rgb, h, w, t, out, ref, sse, f0);
         } else
-            hipLaunchKernelGGL((rgb_to_yuv_kernel<kBytes, kChroma, kSemi, kVec, false>), grid, dim3(256), 0, s, rgb,
+            hipLaunchKernelGGL((rgb_to_yuv_kernel<kBytes, kChroma, kSemi, kVec, false, kLegacyImm>), grid, dim3(256), 0, s, rgb,
                                h, w, t, out, nullptr, nullptr, f0);
     }
 }
@@ -540,20 +640,61 @@ void run(const InArgs &a) {
     launch_in<kBytes, kChroma, kSemi>(a.vec, a.frames, a.yuv, a.h, a.w, a.t, a.out, a.s);
 }
 
-template <int kBytes, int kChroma, bool kSemi>
+template <int kBytes, int kChroma, bool kSemi, bool kLegacyImm = false>
 void run(const OutArgs &a) {
-    if (a.vec) launch_out<kBytes, kChroma, kSemi, true>(a.frames, a.rgb, a.h, a.w, a.t, a.out, a.ref, a.sse, a.s);
-    else launch_out<kBytes, kChroma, kSemi, false>(a.frames, a.rgb, a.h, a.w, a.t, a.out, a.ref, a.sse, a.s);
+    if (a.vec)
+        launch_out<kBytes, kChroma, kSemi, true, kLegacyImm>(a.frames, a.rgb, a.h, a.w, a.t, a.out, a.ref, a.sse, a.s);
+    else
+        launch_out<kBytes, kChroma, kSemi, false, kLegacyImm>(a.frames, a.rgb, a.h, a.w, a.t, a.out, a.ref, a.sse, a.s);
 }
 
-// the five layouts (planar 4:2:0 was refused by conversion_args)
+// the six layouts
 template <int kBytes, typename Args>
 void pick_layout(int chroma, bool semi, const Args &a) {
-    if (chroma == 420) run<kBytes, 420, true>(a);
+    if (chroma == 420 && semi) run<kBytes, 420, true>(a);
+    else if (chroma == 420) run<kBytes, 420, false>(a);
     else if (chroma == 422 && semi) run<kBytes, 422, true>(a);
     else if (chroma == 422) run<kBytes, 422, false>(a);
     else if (semi) run<kBytes, 444, true>(a);
     else run<kBytes, 444, false>(a);
+}
+
+// The vector layout's condition: W % 8 == 0, the float planes 16-byte aligned
+// and the sample buffers (ref may be null) clear of sample_mask: 15 everywhere
+// but in gsvc_rgb_to_i420, which passes 7 (the header comment says why).
+bool vector_path(int w, const float *planes, const void *samples, const void *ref, unsigned sample_mask) {
+    return w % 8 == 0 && ((uintptr_t)planes & 15u) == 0 &&
+           (((uintptr_t)samples | (uintptr_t)ref) & sample_mask) == 0;
+}
+
+int convert_in(const char *what, Serves serves, int frames, const void *yuv, int h, int w,
+               const gsvc_yuv_format *fmt, int chroma, int semi, float *out, void *stream) {
+    FmtDev t;
+    if (const int rc = conversion_args(what, serves, frames, h, w, fmt, chroma, semi, yuv, out, nullptr, nullptr,
+                                       yuv, &t))
+        return rc;
+    const InArgs a{vector_path(w, out, yuv, nullptr, 15u), frames, yuv, h, w, t, out, (hipStream_t)stream};
+    if (fmt->bit_depth == 8) pick_layout<1>(chroma, semi != 0, a);
+    else pick_layout<2>(chroma, semi != 0, a);
+    return check_launch(what);
+}
+
+int convert_out(const char *what, Serves serves, unsigned sample_mask, int frames, const float *rgb, int h, int w,
+                const gsvc_yuv_format *fmt, int chroma, int semi, void *out, const void *ref,
+                unsigned long long *sse, void *stream) {
+    FmtDev t;
+    if (const int rc = conversion_args(what, serves, frames, h, w, fmt, chroma, semi, rgb, out, ref, sse, out, &t))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (ref) {
+        const int rc = dev_zero(sse, (size_t)frames * 3 * sizeof(unsigned long long), s);
+        if (rc) return rc;
+    }
+    const OutArgs a{vector_path(w, rgb, out, ref, sample_mask), frames, rgb, h, w, t, out, ref, sse, s};
+    if (serves == kLegacyI420) run<1, 420, false, true>(a);  // the table as immediates
+    else if (fmt->bit_depth == 8) pick_layout<1>(chroma, semi != 0, a);
+    else pick_layout<2>(chroma, semi != 0, a);
+    return check_launch(what);
 }
 
 }  // namespace
@@ -562,35 +703,39 @@ void pick_layout(int chroma, bool semi, const Args &a) {
 
 using namespace gsvc;
 
+extern "C" int gsvc_yuv_format_table(const gsvc_yuv_format *fmt, long long out[18]) {
+    if (!out) return set_error(GSVC_ERR_ARG, "yuv_format_table: missing buffer");
+    if (const char *bad = table_of(fmt, out)) return set_error(GSVC_ERR_ARG, "yuv_format_table: %s", bad);
+    return GSVC_OK;
+}
+
+extern "C" int gsvc_rgb_to_i420(int frames, const float *rgb, int height, int width, unsigned char *out,
+                                const unsigned char *ref, unsigned long long *sse, void *stream) {
+    return convert_out("rgb_to_i420", kLegacyI420, 7u, frames, rgb, height, width, &kLegacyFormat, 420, 0, out, ref,
+                       sse, stream);
+}
+
+extern "C" int gsvc_yuv420_to_rgb(int frames, const void *yuv, int height, int width,
+                                  const gsvc_yuv_format *fmt, float *out, void *stream) {
+    return convert_in("yuv420_to_rgb", kPlanar420, frames, yuv, height, width, fmt, 420, 0, out, stream);
+}
+
+extern "C" int gsvc_rgb_to_yuv420(int frames, const float *rgb, int height, int width,
+                                  const gsvc_yuv_format *fmt, void *out, const void *ref,
+                                  unsigned long long *sse, void *stream) {
+    return convert_out("rgb_to_yuv420", kPlanar420, 15u, frames, rgb, height, width, fmt, 420, 0, out, ref, sse,
+                       stream);
+}
+
 extern "C" int gsvc_yuv_to_rgb(int frames, const void *yuv, int height, int width, const gsvc_yuv_format *fmt,
                                int chroma, int semi_planar, float *out, void *stream) {
-    FmtDev t;
-    if (const int rc = conversion_args("yuv_to_rgb", frames, height, width, fmt, chroma, semi_planar, yuv, out,
-                                       nullptr, nullptr, yuv, &t))
-        return rc;
-    const bool vec = (width % 8 == 0) && (((uintptr_t)yuv | (uintptr_t)out) & 15u) == 0;
-    const InArgs a{vec, frames, yuv, height, width, t, out, (hipStream_t)stream};
-    if (fmt->bit_depth == 8) pick_layout<1>(chroma, semi_planar != 0, a);
-    else pick_layout<2>(chroma, semi_planar != 0, a);
-    return check_launch("yuv_to_rgb");
+    return convert_in("yuv_to_rgb", kLayouts, frames, yuv, height, width, fmt, chroma, semi_planar, out, stream);
 }
 
 extern "C" int gsvc_rgb_to_yuv(int frames, const float *rgb, int height, int width, const gsvc_yuv_format *fmt,
                                int chroma, int semi_planar, void *out, const void *ref,
                                unsigned long long *sse, void *stream) {
-    FmtDev t;
-    if (const int rc = conversion_args("rgb_to_yuv", frames, height, width, fmt, chroma, semi_planar, rgb, out,
-                                       ref, sse, out, &t))
-        return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (ref) {
-        const int rc = dev_zero(sse, (size_t)frames * 3 * sizeof(unsigned long long), s);
-        if (rc) return rc;
-    }
-    const uintptr_t at = (uintptr_t)rgb | (uintptr_t)out | (uintptr_t)ref;
-    const bool vec = (width % 8 == 0) && (at & 15u) == 0;
-    const OutArgs a{vec, frames, rgb, height, width, t, out, ref, sse, s};
-    if (fmt->bit_depth == 8) pick_layout<1>(chroma, semi_planar != 0, a);
-    else pick_layout<2>(chroma, semi_planar != 0, a);
-    return check_launch("rgb_to_yuv");
+    return convert_out("rgb_to_yuv", kLayouts, 15u, frames, rgb, height, width, fmt, chroma, semi_planar, out, ref,
+                       sse, stream);
 }
+

@@ -70,9 +70,9 @@ _FLAG_DEPTH, _FLAG_MATRIX, _FLAG_FULL = 0x3, 0x10, 0x40
 _CHROMAS = ("420", "422", "444")   # the layout code's bits 0-1
 _LAYOUTS = ("planar", "semi")      # the layout code's bit 4
 _LAYOUT_CHROMA, _LAYOUT_SEMI = 0x3, 0x10
-# the legacy triple's constants (csrc/yuv.hip, csrc/yuv_out.hip: OpenCV's three
-# decimals) in gsvc_yuv_format_table's order: what the layouts beyond planar
-# 4:2:0 compute with at 8-bit bt601 limited range
+# the legacy triple's constants (csrc/yuv.hip, csrc/yuv_conv.hip's kLegacyTable:
+# OpenCV's three decimals) in gsvc_yuv_format_table's order: what every layout
+# computes with at 8-bit bt601 limited range
 _LEGACY_TABLE = (255, 16, 128, 1, 1220542, 1673527, -409993, -852492, 2116026, 269484, 528482, 102760,
                  -155188, -305135, 460324, 460324, -385875, -74448)
 
@@ -87,10 +87,10 @@ class YuvFormat:
     (yuv420p10le), semi-planar with the value in the high bits (the P010
     family: word = value << (16 - bit_depth)).
     ``YuvFormat()`` is the legacy format (planar 4:2:0, 8-bit BT.601 limited
-    range), which keeps OpenCV's arithmetic (csrc/yuv.hip, csrc/yuv_out.hip);
-    every other planar 4:2:0 format takes the exact coefficients of
-    csrc/yuv_fmt.hip, every other chroma or layout
-    csrc/yuv_layout.hip."""
+    range), which keeps OpenCV's constants (csrc/yuv.hip in, csrc/yuv_conv.hip
+    out); every other colour triple takes gsvc_yuv_format_table's exact
+    coefficients, every chroma and layout the same kernels of
+    csrc/yuv_conv.hip."""
     bit_depth: int = 8
     matrix: str = "bt601"
     full_range: bool = False
@@ -122,7 +122,7 @@ class YuvFormat:
 
     @property
     def is_planar420(self) -> bool:
-        """The layout of the four entries of before (csrc/yuv*.hip but yuv_layout.hip)."""
+        """The layout of gsvc_i420_to_rgb / gsvc_rgb_to_i420 and gsvc_yuv420_to_rgb / gsvc_rgb_to_yuv420."""
         return self.chroma == "420" and self.layout == "planar"
 
     @property
@@ -327,7 +327,8 @@ def _join_planes(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, fmt: YuvForm
 
 
 def _yuv_to_rgb_torch(raw: torch.Tensor, h: int, w: int, fmt: YuvFormat) -> torch.Tensor:
-    """csrc/yuv_layout.hip's input arithmetic in torch int64 ops (CPU tensors)."""
+    """The input arithmetic of csrc/yuv_conv.hip (and, for the legacy format, of
+    csrc/yuv.hip) in torch int64 ops (CPU tensors), for one frame."""
     P, yoff, coff, _, cy, crv, cgu, cgv, cbu = fmt.conversion_table()[:9]
     y, u, v = _split_planes(_samples_int64(raw, fmt)[None], h, w, fmt)
     y = (y[0] - yoff).clamp_min(0) * cy + (1 << 19)
@@ -338,7 +339,7 @@ def _yuv_to_rgb_torch(raw: torch.Tensor, h: int, w: int, fmt: YuvFormat) -> torc
 
 
 def _rgb_to_yuv_torch(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: YuvFormat):
-    """csrc/yuv_layout.hip's output arithmetic in torch int64 ops (CPU tensors)."""
+    """csrc/yuv_conv.hip's output arithmetic in torch int64 ops (CPU tensors)."""
     F_, _, H, W = images.shape
     P, yoff, coff = fmt.conversion_table()[:3]
     yr, yg, yb, ur, ug, ub, vr, vg, vb = fmt.conversion_table()[9:]
@@ -361,30 +362,79 @@ def _rgb_to_yuv_torch(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: Yu
     return out, sse
 
 
-def _yuv_to_rgb(yuv: torch.Tensor, height: int, width: int, fmt: YuvFormat) -> torch.Tensor:
-    """``i420_to_rgb`` for a chroma or layout other than planar 4:2:0."""
+def i420_to_rgb(yuv: torch.Tensor, height: int, width: int, fmt: Optional[YuvFormat] = None) -> torch.Tensor:
+    """One frame (its raw bytes: a uint8 tensor of ``fmt.frame_bytes(H, W)``; for
+    a 16-bit format also an int16 tensor of its samples) -> [1, 3, H, W] float
+    RGB in [0, 1] on the tensor's device.  ``fmt`` None or ``YuvFormat()``: 8-bit
+    I420 with OpenCV's BT.601 arithmetic (cv2.cvtColor(COLOR_YUV2RGB_I420) +
+    ToTensor, ``gsvc_i420_to_rgb``, csrc/yuv.hip); any other planar 4:2:0
+    format: ``gsvc_yuv420_to_rgb``; 4:2:2, 4:4:4 and semi-planar frames
+    (``fmt.chroma``, ``fmt.layout``; any height at 4:2:2, any size at 4:4:4):
+    ``gsvc_yuv_to_rgb`` (both csrc/yuv_conv.hip).  A CPU tensor takes the same
+    arithmetic in torch integer ops (the codec's encoder on a host without a
+    GPU)."""
+    fmt = fmt or YuvFormat()
+    if fmt.is_legacy:  # the first entry's checks and wording; the size is the C entry's to refuse
+        if yuv.dtype != torch.uint8:
+            raise RuntimeError("yuv must be a uint8 tensor")
+        if yuv.numel() != height * width * 3 // 2:
+            raise ValueError("yuv must hold one I420 frame of H*W*3/2 bytes")
+        raw = yuv.reshape(-1)
+    else:
+        if not fmt.is_planar420:
+            fmt.check_size(int(height), int(width))
+        elif height <= 0 or width <= 0 or height % 2 or width % 2:
+            raise ValueError("i420_to_rgb: height and width positive and even")
+        raw = _sample_bytes_of(yuv, fmt, fmt.frame_bytes(height, width), "yuv")
     height, width = int(height), int(width)
-    fmt.check_size(height, width)
-    raw = _sample_bytes_of(yuv, fmt, fmt.frame_bytes(height, width), "yuv")
     if not raw.is_cuda:
         return _yuv_to_rgb_torch(raw, height, width, fmt)
     from . import _lib as L
     if not raw.is_contiguous() or raw.data_ptr() % fmt.sample_bytes:
         raw = raw.clone()  # a 16-bit view at an odd address
     out = torch.empty((1, 3, height, width), dtype=torch.float32, device=raw.device)
-    L.call("gsvc_yuv_to_rgb", 1, L.ptr(raw), height, width, fmt._c(), int(fmt.chroma),
-           int(fmt.layout == "semi"), L.ptr(out), L.stream(raw.device))
+    if fmt.is_legacy:
+        L.call("gsvc_i420_to_rgb", L.ptr(raw), height, width, L.ptr(out), L.stream(raw.device))
+    elif fmt.is_planar420:
+        L.call("gsvc_yuv420_to_rgb", 1, L.ptr(raw), height, width, fmt._c(), L.ptr(out), L.stream(raw.device))
+    else:
+        L.call("gsvc_yuv_to_rgb", 1, L.ptr(raw), height, width, fmt._c(), int(fmt.chroma),
+               int(fmt.layout == "semi"), L.ptr(out), L.stream(raw.device))
     return out
 
 
-def _rgb_to_yuv(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: YuvFormat):
-    """``rgb_to_i420`` for a chroma or layout other than planar 4:2:0."""
+def rgb_to_i420(images: torch.Tensor, ref: Optional[torch.Tensor] = None, fmt: Optional[YuvFormat] = None):
+    """Float RGB images [F, 3, H, W] (or [3, H, W]; any values) -> frames as the
+    bytes of a .yuv file, uint8 [F, fmt.frame_bytes(H, W)]: per frame Y, then U
+    and V of half size each way, chroma from the 2x2 block's sum; the inverse of
+    ``i420_to_rgb``.  ``fmt`` None or ``YuvFormat()``: 8-bit I420, BT.601 limited
+    range (``gsvc_rgb_to_i420``); any other planar 4:2:0 format:
+    ``gsvc_rgb_to_yuv420`` (samples above 8 bits as 16-bit little-endian); 4:2:2,
+    4:4:4 and semi-planar output (chroma from the 2x1 block's sum or the pixel
+    itself; U, V interleaved; the P010 family's words): ``gsvc_rgb_to_yuv`` (all
+    three csrc/yuv_conv.hip).  With ``ref`` (source frames, uint8, the output's
+    shape; int16 samples for a 16-bit format) also returns the exact sums of
+    squared sample differences, int64 [F, 3] (Y, U, V).  CUDA tensors take the
+    kernel, CPU tensors the same arithmetic in torch integer ops; the bytes
+    are the same."""
+    if images.dim() == 3:
+        images = images[None]
+    if images.dim() != 4 or images.shape[1] != 3 or not images.is_floating_point():
+        raise ValueError("images must be a float tensor [F, 3, H, W] or [3, H, W]")
+    fmt = fmt or YuvFormat()
     F_, _, H, W = (int(s) for s in images.shape)
-    if F_ <= 0:
-        raise ValueError("rgb_to_i420: at least one frame")
-    fmt.check_size(H, W)
+    if not fmt.is_planar420:
+        if F_ <= 0:
+            raise ValueError("rgb_to_i420: at least one frame")
+        fmt.check_size(H, W)
+    elif F_ <= 0 or H <= 0 or W <= 0 or H % 2 or W % 2:
+        raise ValueError("rgb_to_i420: at least one frame; height and width positive and even")
     size = fmt.frame_bytes(H, W)
-    if ref is not None:
+    if ref is not None and fmt.is_legacy:  # the first entry's check and wording
+        if ref.dtype != torch.uint8 or ref.numel() != F_ * size or ref.device != images.device:
+            raise ValueError(f"ref must hold {F_} I420 frames of {size} bytes (uint8) on the images' device")
+        ref = ref.reshape(-1)
+    elif ref is not None:
         if ref.device != images.device:
             raise ValueError("ref must be on the images' device")
         ref = _sample_bytes_of(ref, fmt, F_ * size, "ref")
@@ -400,181 +450,13 @@ def _rgb_to_yuv(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: YuvForma
         if not ref.is_contiguous() or ref.data_ptr() % fmt.sample_bytes:
             ref = ref.clone()  # a 16-bit view at an odd address
         sse = torch.empty((F_, 3), dtype=torch.int64, device=src.device)
-    L.call("gsvc_rgb_to_yuv", F_, L.ptr(src), H, W, fmt._c(), int(fmt.chroma), int(fmt.layout == "semi"),
-           L.ptr(out), L.ptr(ref), L.ptr(sse), L.stream(src.device))
-    return out if ref is None else (out, sse)
-
-
-def _yuv420_to_rgb_torch(raw: torch.Tensor, h: int, w: int, fmt: YuvFormat) -> torch.Tensor:
-    """csrc/yuv_fmt.hip's input arithmetic in torch int64 ops (CPU tensors)."""
-    P, yoff, coff, _, cy, crv, cgu, cgv, cbu = fmt.table()[:9]
-    s = _samples_int64(raw, fmt)
-    n, cn = h * w, (h // 2) * (w // 2)
-    y = (s[:n].view(h, w) - yoff).clamp_min(0) * cy + (1 << 19)
-    u, v = ((s[n + k * cn:n + (k + 1) * cn].view(h // 2, w // 2) - coff)
-            .repeat_interleave(2, 0).repeat_interleave(2, 1) for k in (0, 1))
-    rgb = torch.stack([y + crv * v, y + cgv * v + cgu * u, y + cbu * u]) >> 20
-    return (rgb.clamp(0, P).to(torch.float32) / torch.tensor(float(P), dtype=torch.float32))[None].contiguous()
-
-
-def i420_to_rgb(yuv: torch.Tensor, height: int, width: int, fmt: Optional[YuvFormat] = None) -> torch.Tensor:
-    """One planar 4:2:0 frame (its raw bytes: a uint8 tensor of
-    ``fmt.frame_bytes(H, W)``; for a 16-bit format also an int16 tensor of
-    H*W*3/2 samples) -> [1, 3, H, W] float RGB in [0, 1] on the tensor's device.
-    ``fmt`` None or ``YuvFormat()``: 8-bit I420 with OpenCV's BT.601 arithmetic
-    (cv2.cvtColor(COLOR_YUV2RGB_I420) + ToTensor, ``gsvc_i420_to_rgb``); any
-    other planar 4:2:0 format: ``gsvc_yuv420_to_rgb`` (csrc/yuv_fmt.hip); 4:2:2,
-    4:4:4 and semi-planar frames (``fmt.chroma``, ``fmt.layout``; any height at
-    4:2:2, any size at 4:4:4): ``gsvc_yuv_to_rgb`` (csrc/yuv_layout.hip).  A CPU
-    tensor takes the same arithmetic in torch integer ops (the codec's encoder
-    on a host without a GPU)."""
-    from . import _lib as L
-    if fmt is not None and not fmt.is_planar420:
-        return _yuv_to_rgb(yuv, height, width, fmt)
-    if fmt is not None and not fmt.is_legacy:
-        if height <= 0 or width <= 0 or height % 2 or width % 2:
-            raise ValueError("i420_to_rgb: height and width positive and even")
-        raw = _sample_bytes_of(yuv, fmt, fmt.frame_bytes(height, width), "yuv")
-        if not raw.is_cuda:
-            return _yuv420_to_rgb_torch(raw, int(height), int(width), fmt)
-        if not raw.is_contiguous() or raw.data_ptr() % fmt.sample_bytes:
-            raw = raw.clone()  # a 16-bit view at an odd address
-        out = torch.empty((1, 3, height, width), dtype=torch.float32, device=raw.device)
-        L.call("gsvc_yuv420_to_rgb", 1, L.ptr(raw), int(height), int(width), fmt._c(), L.ptr(out),
-               L.stream(raw.device))
-        return out
-    if yuv.dtype != torch.uint8:
-        raise RuntimeError("yuv must be a uint8 tensor")
-    if yuv.numel() != height * width * 3 // 2:
-        raise ValueError("yuv must hold one I420 frame of H*W*3/2 bytes")
-    if not yuv.is_cuda:
-        h, w, n, cn = int(height), int(width), height * width, (height // 2) * (width // 2)
-        flat = yuv.reshape(-1).to(torch.int64)
-        y = (flat[:n].view(h, w) - 16).clamp_min(0) * 1220542 + (1 << 19)
-        u, v = ((flat[n + k * cn:n + (k + 1) * cn].view(h // 2, w // 2) - 128)
-                .repeat_interleave(2, 0).repeat_interleave(2, 1) for k in (0, 1))
-        rgb = torch.stack([y + 1673527 * v, y - 852492 * v - 409993 * u, y + 2116026 * u]) >> 20
-        return (rgb.clamp(0, 255).to(torch.float32) / 255.0)[None].contiguous()
-    out = torch.empty((1, 3, height, width), dtype=torch.float32, device=yuv.device)
-    L.call("gsvc_i420_to_rgb", L.ptr(yuv.contiguous()), int(height), int(width), L.ptr(out),
-           L.stream(yuv.device))
-    return out
-
-
-def _rgb_to_i420_torch(images: torch.Tensor, ref: Optional[torch.Tensor]):
-    """csrc/yuv_out.hip's arithmetic in torch integer ops (CPU tensors)."""
-    F_, _, H, W = images.shape
-    c = torch.where(images > 0, images, torch.zeros_like(images))  # NaN, -0 -> 0
-    c = torch.where(c < 1, c, torch.ones_like(c))
-    q = (c * 255.0 + 0.5).to(torch.int32)  # fp32: one rounding per op, then truncation
-    R, G, B = q[:, 0], q[:, 1], q[:, 2]
-    Y = (269484 * R + 528482 * G + 102760 * B + ((16 << 20) + (1 << 19))) >> 20
-    Rs, Gs, Bs = (t.view(F_, H // 2, 2, W // 2, 2).sum(dim=(2, 4), dtype=torch.int32) for t in (R, G, B))
-    U = (-155188 * Rs - 305135 * Gs + 460324 * Bs + ((128 << 22) + (1 << 21))) >> 22
-    V = (460324 * Rs - 385875 * Gs - 74448 * Bs + ((128 << 22) + (1 << 21))) >> 22
-    out = torch.cat([t.clamp(0, 255).to(torch.uint8).reshape(F_, -1) for t in (Y, U, V)], dim=1)
-    if ref is None:
-        return out
-    d = out.to(torch.int64) - ref.to(torch.int64)
-    d = d * d
-    n, cn = H * W, H * W // 4
-    sse = torch.stack([d[:, :n].sum(1), d[:, n:n + cn].sum(1), d[:, n + cn:].sum(1)], dim=1)
-    return out, sse
-
-
-def _rgb_to_yuv420_torch(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: YuvFormat):
-    """csrc/yuv_fmt.hip's output arithmetic in torch int64 ops (CPU tensors)."""
-    F_, _, H, W = images.shape
-    P, yoff, coff = fmt.table()[:3]
-    yr, yg, yb, ur, ug, ub, vr, vg, vb = fmt.table()[9:]
-    c = torch.where(images > 0, images, torch.zeros_like(images))  # NaN, -0 -> 0
-    c = torch.where(c < 1, c, torch.ones_like(c))
-    q = (c * float(P) + 0.5).to(torch.int64)  # fp32: one rounding per op, then truncation
-    R, G, B = q[:, 0], q[:, 1], q[:, 2]
-    Y = (yr * R + yg * G + yb * B + ((yoff << 20) + (1 << 19))) >> 20
-    Rs, Gs, Bs = (t.view(F_, H // 2, 2, W // 2, 2).sum(dim=(2, 4)) for t in (R, G, B))
-    U = (ur * Rs + ug * Gs + ub * Bs + ((coff << 22) + (1 << 21))) >> 22
-    V = (vr * Rs + vg * Gs + vb * Bs + ((coff << 22) + (1 << 21))) >> 22
-    planes = torch.cat([t.clamp(0, P).reshape(F_, -1) for t in (Y, U, V)], dim=1)
-    out = _samples_bytes(planes, fmt)
-    if ref is None:
-        return out
-    d = planes - _samples_int64(ref, fmt).view(F_, -1)
-    d = d * d
-    n, cn = H * W, H * W // 4
-    sse = torch.stack([d[:, :n].sum(1), d[:, n:n + cn].sum(1), d[:, n + cn:].sum(1)], dim=1)
-    return out, sse
-
-
-def _rgb_to_yuv420(images: torch.Tensor, ref: Optional[torch.Tensor], fmt: YuvFormat):
-    """``rgb_to_i420`` for a format other than the legacy one."""
-    F_, _, H, W = (int(s) for s in images.shape)
-    size = fmt.frame_bytes(H, W)
-    if ref is not None:
-        if ref.device != images.device:
-            raise ValueError("ref must be on the images' device")
-        ref = _sample_bytes_of(ref, fmt, F_ * size, "ref")
-    if not images.is_cuda:
-        return _rgb_to_yuv420_torch(images.detach().float(), ref, fmt)
-    from . import _lib as L
-    src = images.detach()
-    if src.dtype is not torch.float32 or not src.is_contiguous():
-        src = src.float().contiguous()
-    out = torch.empty((F_, size), dtype=torch.uint8, device=src.device)
-    sse = None
-    if ref is not None:
-        if not ref.is_contiguous() or ref.data_ptr() % fmt.sample_bytes:
-            ref = ref.clone()  # a 16-bit view at an odd address
-        sse = torch.empty((F_, 3), dtype=torch.int64, device=src.device)
-    L.call("gsvc_rgb_to_yuv420", F_, L.ptr(src), H, W, fmt._c(), L.ptr(out), L.ptr(ref), L.ptr(sse),
-           L.stream(src.device))
-    return out if ref is None else (out, sse)
-
-
-def rgb_to_i420(images: torch.Tensor, ref: Optional[torch.Tensor] = None, fmt: Optional[YuvFormat] = None):
-    """Float RGB images [F, 3, H, W] (or [3, H, W]; any values) -> planar 4:2:0
-    frames as the bytes of a .yuv file, uint8 [F, fmt.frame_bytes(H, W)]: per
-    frame Y, then U and V of half size each way, chroma from the 2x2 block's
-    sum; the inverse of ``i420_to_rgb``.  ``fmt`` None or ``YuvFormat()``: 8-bit
-    I420, BT.601 limited range (``gsvc_rgb_to_i420``, csrc/yuv_out.hip); any
-    other format: ``gsvc_rgb_to_yuv420`` (csrc/yuv_fmt.hip; samples above 8 bits
-    as 16-bit little-endian); 4:2:2, 4:4:4 and semi-planar output (chroma from
-    the 2x1 block's sum or the pixel itself; U, V interleaved; the P010 family's
-    words): ``gsvc_rgb_to_yuv`` (csrc/yuv_layout.hip).  With ``ref`` (source frames, uint8, the output's
-    shape; int16 samples for a 16-bit format) also returns the exact sums of
-    squared sample differences, int64 [F, 3] (Y, U, V).  CUDA tensors take the
-    kernel, CPU tensors the same arithmetic in torch integer ops; the bytes
-    are the same."""
-    if images.dim() == 3:
-        images = images[None]
-    if images.dim() != 4 or images.shape[1] != 3 or not images.is_floating_point():
-        raise ValueError("images must be a float tensor [F, 3, H, W] or [3, H, W]")
-    F_, _, H, W = (int(s) for s in images.shape)
-    if fmt is not None and not fmt.is_planar420:
-        return _rgb_to_yuv(images, ref, fmt)
-    if F_ <= 0 or H <= 0 or W <= 0 or H % 2 or W % 2:
-        raise ValueError("rgb_to_i420: at least one frame; height and width positive and even")
-    if fmt is not None and not fmt.is_legacy:
-        return _rgb_to_yuv420(images, ref, fmt)
-    size = H * W * 3 // 2
-    if ref is not None:
-        if ref.dtype != torch.uint8 or ref.numel() != F_ * size or ref.device != images.device:
-            raise ValueError(f"ref must hold {F_} I420 frames of {size} bytes (uint8) on the images' device")
-        ref = ref.reshape(F_, size)
-    if not images.is_cuda:
-        return _rgb_to_i420_torch(images.detach().float(), ref)
-    from . import _lib as L
-    src = images.detach()
-    if src.dtype is not torch.float32 or not src.is_contiguous():
-        src = src.float().contiguous()
-    out = torch.empty((F_, size), dtype=torch.uint8, device=src.device)
-    sse = None
-    if ref is not None:
-        if not ref.is_contiguous():
-            ref = ref.contiguous()
-        sse = torch.empty((F_, 3), dtype=torch.int64, device=src.device)
-    L.call("gsvc_rgb_to_i420", F_, L.ptr(src), H, W, L.ptr(out), L.ptr(ref), L.ptr(sse),
-           L.stream(src.device))
+    tail = (L.ptr(out), L.ptr(ref), L.ptr(sse), L.stream(src.device))
+    if fmt.is_legacy:
+        L.call("gsvc_rgb_to_i420", F_, L.ptr(src), H, W, *tail)
+    elif fmt.is_planar420:
+        L.call("gsvc_rgb_to_yuv420", F_, L.ptr(src), H, W, fmt._c(), *tail)
+    else:
+        L.call("gsvc_rgb_to_yuv", F_, L.ptr(src), H, W, fmt._c(), int(fmt.chroma), int(fmt.layout == "semi"), *tail)
     return out if ref is None else (out, sse)
 
 

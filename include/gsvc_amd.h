@@ -749,9 +749,10 @@ int gsvc_rasterize_backward(
  * OpenCV's COLOR_YUV2RGB_I420 fixed-point BT.601 arithmetic.  H, W even. */
 int gsvc_i420_to_rgb(const unsigned char *yuv, int height, int width, float *out, void *stream);
 
-/* Video output (not in the reference, which writes no YUV): the inverse of the
- * above for a batch.  rgb [frames][3][H][W] fp32 (any values), out frames *
- * (H*W*3/2) bytes: per frame Y (H*W), U, V ((H/2)*(W/2) each).  Per channel
+/* Video output (not in the reference, which writes no YUV; csrc/yuv_conv.hip, as
+ * every conversion entry below): the inverse of the above for a batch.  rgb
+ * [frames][3][H][W] fp32 (any values), out frames * (H*W*3/2) bytes: per frame
+ * Y (H*W), U, V ((H/2)*(W/2) each).  Per channel
  * q = (int)(min(max(x, 0), 1) * 255 + 0.5) (NaN -> 0); Y = (269484 R + 528482 G
  * + 102760 B + (16 << 20) + (1 << 19)) >> 20; with Rs, Gs, Bs the sums of q over
  * a 2x2 block, U = (-155188 Rs - 305135 Gs + 460324 Bs + (128 << 22) + (1 << 21))
@@ -761,11 +762,14 @@ int gsvc_i420_to_rgb(const unsigned char *yuv, int height, int width, float *out
  * receives the exact integer sums of squared byte differences (the entry zeroes
  * sse on the stream first).  H, W even, > 0.  Any alignment: W % 8 == 0 with rgb
  * 16-byte and out / ref 8-byte aligned takes the vector kernel, everything else
- * the bytewise one; both write the same bytes. */
+ * the bytewise one; both write the same bytes.  GSVC_ERR_ARG before any launch
+ * for frames <= 0, a size that is not positive and even, a missing buffer, ref
+ * without sse, and a frame of more than 2^31 - 1 blocks of 256 chroma samples
+ * (which no allocation can hold). */
 int gsvc_rgb_to_i420(int frames, const float *rgb, int height, int width, unsigned char *out,
                      const unsigned char *ref, unsigned long long *sse, void *stream);
 
-/* Pixel formats beyond the two entries above (csrc/yuv_fmt.hip):
+/* Pixel formats beyond the two entries above (csrc/yuv_conv.hip):
  * planar YUV 4:2:0 of 8, 10, 12 or 16 bits per sample, BT.601 or BT.709, limited
  * or full range.  Samples of more than 8 bits are 16-bit little-endian words with
  * the value in the low bits (yuv420p10le, ...12le, ...16le); planes Y, U, V.
@@ -817,7 +821,7 @@ int gsvc_rgb_to_yuv420(int frames, const float *rgb, int height, int width,
                        const gsvc_yuv_format *fmt, void *out, const void *ref,
                        unsigned long long *sse, void *stream);
 
-/* Chroma layouts beyond planar 4:2:0 (csrc/yuv_layout.hip), for
+/* Chroma layouts beyond planar 4:2:0 (csrc/yuv_conv.hip), for
  * every gsvc_yuv_format: chroma = 420, 422 or 444; semi_planar = 0: planes Y, U,
  * V; 1: plane Y, then one plane of interleaved U, V pairs, U first (NV12 / NV16 /
  * NV24).  Samples per frame: Y H*W; U and V each (H/2)*(W/2) at 420 (H, W even),

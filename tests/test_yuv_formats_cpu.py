@@ -1,4 +1,4 @@
-"""CPU: the pixel formats beyond 8-bit BT.601 limited range (csrc/yuv_fmt.hip,
+"""CPU: the pixel formats beyond 8-bit BT.601 limited range (csrc/yuv_conv.hip,
 ``video.YuvFormat``): the coefficient table against its formula, the premises
 of the arithmetic, known answers, the round trip, the torch dispatch of both
 conversions against the numpy statement (tests/yuv_format_cases.py), the

@@ -1,4 +1,4 @@
-"""GPU: gsvc_yuv420_to_rgb / gsvc_rgb_to_yuv420 (csrc/yuv_fmt.hip) byte for byte
+"""GPU: gsvc_yuv420_to_rgb / gsvc_rgb_to_yuv420 (csrc/yuv_conv.hip) byte for byte
 against the numpy statement of their arithmetic (tests/yuv_format_cases.py) on
 both layouts, the exact 64-bit SSE, ``decode_frames(output="i420", fmt=...)``,
 a 10-bit file through ``decode_video`` on both devices, one 1080p case, and

@@ -1,4 +1,4 @@
-"""CPU: 4:2:2, 4:4:4 and semi-planar YUV (csrc/yuv_layout.hip, the ``chroma`` and
+"""CPU: 4:2:2, 4:4:4 and semi-planar YUV (csrc/yuv_conv.hip, the ``chroma`` and
 ``layout`` of ``video.YuvFormat``): the descriptor and ffmpeg's names, the
 premises of the arithmetic per layout, known answers in every layout, the
 byte permutation nv12 is of I420, the 4:4:4 round trip, the torch dispatch of

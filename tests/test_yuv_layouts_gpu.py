@@ -1,4 +1,4 @@
-"""GPU: gsvc_yuv_to_rgb / gsvc_rgb_to_yuv (csrc/yuv_layout.hip) byte for byte
+"""GPU: gsvc_yuv_to_rgb / gsvc_rgb_to_yuv (csrc/yuv_conv.hip) byte for byte
 against the numpy statement of their arithmetic (tests/yuv_layout_cases.py) in
 the five layouts beyond planar 4:2:0, on the vector and the fallback layout of
 the work, the exact 64-bit SSE, ``decode_frames(output="yuv", fmt=...)``, a

@@ -1,7 +1,8 @@
-"""GPU: gsvc_rgb_to_i420 (csrc/yuv_out.hip) bit-exact against the numpy
+"""GPU: gsvc_rgb_to_i420 (csrc/yuv_conv.hip) bit-exact against the numpy
 statement of its arithmetic (tests/yuv_cases.py) on both layouts, its exact
 integer SSE, ``decode_frames(output="i420")`` and ``decode_video`` from a file
-(batches that cut GOPs, the two pinned buffers reused, frame ranges, PSNR)."""
+(batches that cut GOPs, the two pinned buffers reused, frame ranges, PSNR);
+the entry's 8-byte alignment rule and a partial last block."""
 import numpy as np
 import pytest
 import torch
@@ -104,6 +105,71 @@ def test_sse_of_extreme_planes(cuda):
     want = Y.rgb_to_i420(np.zeros((2, 3, h, w), np.float32))
     assert np.array_equal(got.cpu().numpy(), want)
     assert np.array_equal(sse.cpu().numpy(), Y.sse(want, ref.cpu().numpy(), h, w))
+
+
+# --------------------------------------------------------------------------
+# the entry's own alignment rule: rgb 16-byte, out and ref 8-byte (every other
+# conversion entry asks 16 of its sample buffers; the rule is an argument of
+# the code they share)
+
+def _guarded(nbytes, offset, dev, fill=None):
+    """``nbytes`` at ``offset`` into a 16-byte aligned allocation of 0xA5 bytes."""
+    buf = torch.full((offset + nbytes + 16,), 0xA5, dtype=torch.uint8, device=dev)
+    assert buf.data_ptr() % 16 == 0
+    view = buf[offset:offset + nbytes]
+    if fill is not None:
+        view.copy_(torch.from_numpy(fill).to(dev).view(-1))
+    return buf, view
+
+
+def _guards_intact(buf, offset, nbytes):
+    host = buf.cpu().numpy()
+    return bool((host[:offset] == 0xA5).all() and (host[offset + nbytes:] == 0xA5).all())
+
+
+def _check_offsets(cuda, f, h, w, kind, offsets):
+    size = h * w * 3 // 2
+    x = Y.values(kind, f, h, w, seed=3)
+    want = Y.rgb_to_i420(x)
+    ref = Y.reference_frames(f, h, w, seed=3)
+    e = Y.sse(want, ref, h, w)
+    xd = torch.from_numpy(x).to(cuda)
+    assert xd.data_ptr() % 16 == 0
+    for off in offsets:
+        for with_ref in (False, True):
+            buf, out = _guarded(f * size, off, cuda)
+            assert out.data_ptr() % 16 == off
+            if with_ref:
+                rbuf, rd = _guarded(f * size, off, cuda, fill=ref)
+                sse = torch.full((f, 3), -0x123456789, dtype=torch.int64, device=cuda)
+                _call(xd, out, rd, sse)
+                assert np.array_equal(sse.cpu().numpy(), e), (h, w, f, kind, off)
+                assert _guards_intact(rbuf, off, f * size) and np.array_equal(rd.cpu().numpy().reshape(f, size), ref)
+            else:
+                _call(xd, out)
+            assert np.array_equal(out.cpu().numpy().reshape(f, size), want), (h, w, f, kind, off, with_ref)
+            assert _guards_intact(buf, off, f * size), (h, w, f, kind, off, with_ref)
+
+
+@pytest.mark.parametrize("shape", [(4, 8), (2, 16), (18, 24), (16, 520)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_out_and_ref_at_8_and_4_byte_offsets(cuda, shape):
+    """Offset 8 takes the vector layout (W % 8 == 0, rgb 16-byte, out and ref
+    8-byte aligned), offset 4 the bytewise one; same bytes, same sums, nothing
+    written outside."""
+    h, w = shape
+    if shape == (18, 24):  # the case the 8-byte rule exists for: frame 1 starts 8 mod 16
+        assert h * w * 3 // 2 == 648 and 648 % 16 == 8
+    for f in Y.FRAMES:
+        for kind in ("uniform", "special"):
+            _check_offsets(cuda, f, h, w, kind, (8, 4))
+
+
+def test_partial_last_block_of_the_bytewise_layout(cuda):
+    """34x258: W % 8 = 2, so one lane per 2x2 block: 2193 units are 8 blocks of
+    256 and one of 145, and there is no stride loop to hide behind."""
+    h, w = 34, 258
+    assert w % 8 == 2 and (h // 2) * (w // 2) == 2193 == 8 * 256 + 145
+    _check_offsets(cuda, 2, h, w, "uniform", (0,))
 
 
 # --------------------------------------------------------------------------

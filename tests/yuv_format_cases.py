@@ -1,4 +1,4 @@
-"""The numpy statement of csrc/yuv_fmt.hip's arithmetic (include/gsvc_amd.h:
+"""The numpy statement of csrc/yuv_conv.hip's arithmetic (include/gsvc_amd.h:
 float32 ops in the stated order, int64 afterwards), and the formats, shapes and
 value classes its tests share.  Imports nothing from the package."""
 import math

@@ -1,4 +1,4 @@
-"""The numpy statement of csrc/yuv_layout.hip's arithmetic (DESIGN.md §13f:
+"""The numpy statement of csrc/yuv_conv.hip's arithmetic (DESIGN.md §13f:
 yuv_format_cases' formulas with the chroma block generalised to 2x2, 2x1 and
 1x1, planar and semi-planar frames, the P010 family's words), and the layouts,
 shapes and value classes its tests share.  A layout is (chroma, layout) with
@@ -23,7 +23,7 @@ FRAMES = [1, 3]
 # past one 256-lane block's units)
 SHAPES = [(2, 2), (1, 2), (1, 1), (3, 5), (3, 6), (6, 10), (4, 8), (18, 24), (16, 520)]
 
-# the legacy kernels' constants (csrc/yuv.hip, csrc/yuv_out.hip) in
+# the legacy kernels' constants (csrc/yuv.hip, csrc/yuv_conv.hip) in
 # gsvc_yuv_format_table's order: the legacy triple's table in every layout
 LEGACY_TABLE = [255, 16, 128, 1, 1220542, 1673527, -409993, -852492, 2116026, 269484, 528482, 102760,
                 -155188, -305135, 460324, 460324, -385875, -74448]

@@ -28,15 +28,16 @@ warm-up of every shape; the variants of one comparison alternate window by
 window, so drift in the shared host hits both.  Fails without a HIP device.
 
 With ``--format DEPTH:MATRIX:RANGE`` the session measures that
-pixel format's kernels (csrc/yuv_fmt.hip) against the legacy 8-bit ones instead,
+pixel format (csrc/yuv_conv.hip's kernels with the format's table) against the legacy
+8-bit one (the same kernels with the legacy constants) instead,
 variant against variant in alternating windows: the output conversion alone
 (without and with a reference) and behind ``render_frames_sum``, and the input
 conversion per frame.  The yardstick is the legacy kernel's achieved bytes per
 second in the same session, each kernel over its own algorithmic bytes per
 pixel (12 + 1.5 samples' bytes, + 1.5 samples' with a reference).  With
 ``--format DEPTH:MATRIX:RANGE:CHROMA:LAYOUT`` (several may be
-given) the kernels are csrc/yuv_layout.hip's and the yardstick is the planar
-4:2:0 kernel of the same depth, matrix and range: 12 + 1.5 / 2 / 3 samples' bytes
+given) the kernels are the same source's instances of that layout and the yardstick is the
+planar 4:2:0 instance of the same depth, matrix and range: 12 + 1.5 / 2 / 3 samples' bytes
 per pixel at 4:2:0 / 4:2:2 / 4:4:4."""
 import argparse
 import json
@@ -234,7 +235,7 @@ def _parse_format(text):
 
 
 def _host_i420(rgb):
-    """csrc/yuv_out.hip's arithmetic in numpy: what a user ran on the host."""
+    """gsvc_rgb_to_i420's arithmetic (csrc/yuv_conv.hip) in numpy: what a user ran on the host."""
     f, _, h, w = rgb.shape
     c = np.fmin(np.fmax(rgb, np.float32(0)), np.float32(1))
     q = (c * np.float32(255) + np.float32(0.5)).astype(np.int32)
