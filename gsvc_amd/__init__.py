@@ -87,6 +87,16 @@ NDRasterizeGaussians = _deprecated("NDRasterizeGaussians", rasterize_gaussians,
                                    "rasterize_gaussians")
 SphericalHarmonics = _deprecated("SphericalHarmonics", spherical_harmonics, "spherical_harmonics")
 
+def __getattr__(name):
+    # gsvc_amd.YuvLoss: the weighted Y/U/V training loss's spec, from
+    # gsvc_amd.video on first use (``python -m gsvc_amd.video`` must not find
+    # the module imported already)
+    if name == "YuvLoss":
+        from .video import YuvLoss
+        return YuvLoss
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 __all__ = [
     "__version__",
     "project_gaussians",

@@ -411,7 +411,7 @@ def _decode(args) -> dict:
 
 def _encode(args) -> dict:
     from .compress import compress_video
-    from .video import load_yuv_frames
+    from .video import load_yuv_frames, yuv_loss_of_arguments
     state = torch.load(args.models, map_location="cpu")
     count = sum(1 for k in state if k.startswith("frame_"))
     fmt = format_of_arguments(args)
@@ -423,7 +423,8 @@ def _encode(args) -> dict:
     res = compress_video(state, [by_index[i] for i in range(count)], K_frames=k_frames,
                          iterations=args.iterations, lr=args.lr, device=args.device,
                          delta_base=args.delta_base, seed=args.seed, entropy=args.entropy,
-                         fused=args.fused, run=args.run_length)
+                         fused=args.fused, run=args.run_length, loss_type=args.loss_type,
+                         yuv_loss=yuv_loss_of_arguments(args))
     size = write_video(args.out, res["streams"], fps=(args.fps_num, args.fps_den), fmt=fmt)
     return {"frames": count, "file_bytes": size, "k_frames": k_frames,
             "bpp": round(8.0 * sum(len(s) for s in res["streams"]) / (count * args.width * args.height), 6),
@@ -469,6 +470,11 @@ def main(argv=None) -> dict:
                    help="with --fused: K iterations per call, the best state kept on the device")
     p.add_argument("--delta_base", choices=["overfit", "decoded"], default="decoded",
                    help="decoded (default): the file decodes to what training measured")
+    p.add_argument("--loss_type", default="L2",
+                   help="L2 (default), L1, or YUV: the weighted Y/U/V loss in src's colour space and chroma "
+                        "(--matrix --full_range --chroma --pix_fmt)")
+    p.add_argument("--loss_weights", default=None, metavar="WY,WU,WV",
+                   help="plane weights of --loss_type YUV (default 6,1,1)")
     p.add_argument("--fps_num", type=int, default=30)
     p.add_argument("--fps_den", type=int, default=1)
     add_format_arguments(p)  # of src; stored in the file

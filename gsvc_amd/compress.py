@@ -79,7 +79,8 @@ class _QuantStepArgs(ctypes.Structure):
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
                 ("train_workspace", ctypes.c_void_p), ("train_workspace_bytes", ctypes.c_size_t),
                 ("det_workspace", ctypes.c_void_p), ("det_workspace_bytes", ctypes.c_size_t),
-                ("det_capacity", ctypes.c_longlong), ("stream", ctypes.c_void_p)]
+                ("det_capacity", ctypes.c_longlong), ("stream", ctypes.c_void_p),
+                ("loss_yuv", ctypes.c_void_p), ("loss_chroma", ctypes.c_int)]
 
 
 class _QuantRunArgs(ctypes.Structure):
@@ -105,8 +106,10 @@ class BoundQuantStep:
     hyper-parameters, flags and stream (``train.BoundStep`` is the model).  The
     owner rebuilds it when a bound tensor object or storage changes."""
 
-    def __init__(self, params, tables, bound, prev, background, H, W, loss_type, vq, state):
+    def __init__(self, params, tables, bound, prev, background, H, W, loss_type, vq, state, *,
+                 yuv_loss=None):
         xyz, chol, feat, scale, beta = params
+        self.loss_type, self.yuv_loss = loss_type, yuv_loss  # (the owner rebuilds when either changes)
         n = xyz.shape[0]
         self.tensors = (*params, *tables, bound, *(prev or ()), background, *state)
         self.ids = tuple(map(id, self.tensors))
@@ -139,7 +142,7 @@ class BoundQuantStep:
             a.p_features = T._f32_ptr(prev[2], "p_features_dc", 3 * n)
         a.background = T._f32_ptr(background, "background", 3)
         a.img_height, a.img_width = self.H, self.W
-        a.loss_kind = T.LOSS_KIND[loss_type]
+        self.loss_words = T.loss_args(a, loss_type, yuv_loss, self.H, self.W)
         a.adan_state = ctypes.addressof(self.state)
         a.adan_hparams = ctypes.addressof(self.hp)
         a.decay, a.eps, a.commitment_weight = vq.decay, vq.eps, vq.commitment_weight
@@ -352,6 +355,13 @@ class _QuantFrame(nn.Module):
     def __init__(self, loss_type="L2", **kwargs):
         super().__init__()
         self.loss_type = loss_type
+        # loss_type "YUV": the weighted Y/U/V loss's spec (video.YuvLoss; None: YuvLoss())
+        self.yuv_loss = kwargs.get("yuv_loss")
+        if loss_type == "YUV":
+            if self.yuv_loss is None:
+                from .video import YuvLoss
+                self.yuv_loss = YuvLoss()
+            self.yuv_loss.check_size(kwargs["H"], kwargs["W"])
         self.init_num_points = n = kwargs["num_points"]
         self.H, self.W = kwargs["H"], kwargs["W"]
         self.BLOCK_W, self.BLOCK_H = kwargs["BLOCK_W"], kwargs["BLOCK_H"]
@@ -471,7 +481,7 @@ class _QuantFrame(nn.Module):
         render_pkg = self.forward_quantize()
         image = render_pkg["render"]
         loss = loss_fn(image.squeeze(0), gt_image.squeeze(0), self.loss_type,
-                       lambda_value=0) + render_pkg["vq_loss"]
+                       lambda_value=0, yuv_loss=self.yuv_loss) + render_pkg["vq_loss"]
         loss.backward()
         with torch.no_grad():
             mse_loss = F.mse_loss(image, gt_image)
@@ -487,7 +497,7 @@ class _QuantFrame(nn.Module):
         if not self.quantize:
             raise RuntimeError("train_iter_quantize_fused: the model was built with quantize=False")
         if self.loss_type not in T.LOSS_KIND:
-            raise ValueError("train_iter_quantize_fused supports the L2 and L1 losses, not "
+            raise ValueError("train_iter_quantize_fused supports the L2 and L1 losses and the YUV loss, not "
                              f"{self.loss_type!r}")
         opt = self.optimizer
         if not isinstance(opt, Adan):
@@ -577,10 +587,10 @@ class _QuantFrame(nn.Module):
         tables = (vq.codebooks, vq.cluster_size, vq.embed_avg)
         bound = (*params, *tables, self.cholesky_bound, *(self._prev() or ()), self.background, *state)
         bs = self.__dict__.get("_bound_quant_step")
-        if bs is None or bs.loss_kind != T.LOSS_KIND[self.loss_type] or not bs.matches(bound, vq):
+        if (bs is None or bs.loss_type != self.loss_type or bs.yuv_loss is not self.yuv_loss
+                or not bs.matches(bound, vq)):
             bs = BoundQuantStep(params, tables, self.cholesky_bound, self._prev(), self.background,
-                                self.H, self.W, self.loss_type, vq, state)
-            bs.loss_kind = T.LOSS_KIND[self.loss_type]
+                                self.H, self.W, self.loss_type, vq, state, yuv_loss=self.yuv_loss)
             self.__dict__["_bound_quant_step"] = bs
         return bs, gt
 
@@ -589,8 +599,10 @@ class _QuantFrame(nn.Module):
         returns (loss, psnr), the loss a host scalar tensor.  The model's Adan
         object keeps the state, the step counter and the learning rate, and the
         scheduler steps, so this and ``train_iter_quantize`` interleave at any
-        iteration.  HIP devices, Adan, 16x16 blocks and the L2 / L1 losses only:
-        anything else raises (nothing falls back to the op-by-op method)."""
+        iteration.  HIP devices, Adan, 16x16 blocks and the L2 / L1 / YUV losses
+        only: anything else raises (nothing falls back to the op-by-op method).
+        With the YUV loss the returned loss is that loss plus the VQ term; the
+        PSNR is still the RGB one."""
         mse, mae, s0, s1 = self._fused_step(gt_image)
         opt = self.optimizer
         opt._opt_called = True  # the step ran: keeps StepLR's call-order check quiet
@@ -599,7 +611,7 @@ class _QuantFrame(nn.Module):
         vq = self.features_dc_quantizer
         n = self._xyz.shape[0]
         loss = torch.empty(())
-        loss.numpy()[...] = ((mae if self.loss_type == "L1" else mse)
+        loss.numpy()[...] = ((mse if self.loss_type == "L2" else mae)  # (YUV: word 1 is that loss)
                              + vq.commitment_weight * (s0 + s1) / (3 * n))
         psnr = 10 * math.log10(1.0 / mse)
         return loss, psnr
@@ -615,7 +627,9 @@ class _QuantFrame(nn.Module):
         reference's best state on the device: iteration i of this run has the
         index ``best.seen + i``.  Interleaves with ``train_iter_quantize_fused``
         and ``train_iter_quantize`` at any iteration; the same restrictions,
-        raised before anything has changed."""
+        raised before anything has changed.  With the YUV loss the losses are
+        that loss plus the VQ term, while the best state on the device is still
+        chosen by the RGB mean squared error (the PSNR's)."""
         params = self._fused_tensors(gt_image)
         k = int(iterations)
         if k < 1:
@@ -643,7 +657,7 @@ class _QuantFrame(nn.Module):
         if best is not None:
             best.seen += k
         n = self._xyz.shape[0]
-        pick = 1 if self.loss_type == "L1" else 0
+        pick = 0 if self.loss_type == "L2" else 1  # (L1, YUV: word 1)
         losses, psnrs = [], []
         for w in words:
             losses.append(float(np.float32(w[pick] + vq.commitment_weight * (w[2] + w[3]) / (3 * n))))
@@ -952,7 +966,8 @@ def _load_overfit(model, cur: dict, prev: Optional[dict]) -> None:
 def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: Sequence[int] = (1,),
                    iterations: int = 30000, lr: float = 1e-3, device="cuda:0", loss_type="L2",
                    delta_base: str = "overfit", seed: Optional[int] = None, entropy: bool = False,
-                   segment: int = 32, fused: bool = False, run: Optional[int] = None) -> dict:
+                   segment: int = 32, fused: bool = False, run: Optional[int] = None,
+                   yuv_loss=None) -> dict:
     """Fine-tune every overfit frame model of ``state_dict`` (``frame_<i>`` ->
     {_xyz, _cholesky, _features_dc}, i from 1) under quantization against
     ``frames`` ([1,3,H,W] each) and encode it: frames listed in ``K_frames``
@@ -971,7 +986,9 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
     does.  With ``entropy`` the streams are entropy-coded (version 2, segments
     of ``segment`` splats) and "bpp_coded" gives their ``8 * len / (H * W)``.
     ``fused`` runs every iteration as ``train_iter_quantize_fused`` (one C call;
-    HIP devices and the L2 / L1 losses only -- anything else raises).  With
+    HIP devices and the L2 / L1 / YUV losses only -- anything else raises;
+    ``loss_type="YUV"`` trains against the weighted Y/U/V loss of ``yuv_loss``,
+    a video.YuvLoss, while the best state is still the best RGB PSNR's).  With
     ``run=K`` (``fused`` only) a frame is trained in runs of K iterations, one
     ``train_run_quantize_fused`` call each and a last shorter one, and the best
     state is kept on the device (``QuantBestState``) instead of a host
@@ -996,7 +1013,8 @@ def compress_video(state_dict: dict, frames: Sequence[torch.Tensor], K_frames: S
         gt = gt.to(device)
         H, W = gt.shape[-2], gt.shape[-1]
         cls = GaussianVideoFrameQ if key else GaussianVideoDelta
-        model = cls(loss_type=loss_type, opt_type="adan", num_points=cur["_xyz"].shape[0], H=H, W=W,
+        model = cls(loss_type=loss_type, yuv_loss=yuv_loss, opt_type="adan",
+                    num_points=cur["_xyz"].shape[0], H=H, W=W,
                     BLOCK_H=16, BLOCK_W=16, device=device, lr=lr, quantize=True).to(device)
         prev = None
         if not key:

@@ -53,6 +53,11 @@ int check_launch(const char *what);
 // GSVC_ERR_CAPTURE when stream s is capturing a graph (entries with host-indexed
 // workspace parity; include/gsvc_amd.h conventions), else GSVC_OK
 int refuse_capture(hipStream_t s, const char *what);
+// train.hip: the training step's loss arguments (loss_kind 0, 1, or 2 with the
+// host words loss_yuv, a chroma code and a size it fits), GSVC_ERR_ARG with the
+// reason otherwise
+int loss_kind_check(const char *what, int loss_kind, const float *loss_yuv, int loss_chroma,
+                    unsigned img_height, unsigned img_width);
 // hipMemsetAsync(p, 0, bytes, s) / a device-to-device hipMemcpyAsync as one
 // kernel of this library (errors.hip): the HIP runtime torch loads (ROCm 7.0)
 // replays graph-captured memset nodes wrongly once other work has run on the

@@ -460,8 +460,8 @@ static int quant_step_check(const gsvc_quant_train_args *a, const char *what) {
         return set_error(GSVC_ERR_ARG, "%s: p_xyz, p_cholesky, p_features go together", what);
     if (!a->background || !a->gt) return set_error(GSVC_ERR_ARG, "%s: null background / gt", what);
     if (a->img_height == 0 || a->img_width == 0) return set_error(GSVC_ERR_ARG, "%s: bad sizes", what);
-    if (a->loss_kind != 0 && a->loss_kind != 1)
-        return set_error(GSVC_ERR_ARG, "%s: loss_kind must be 0 (L2) or 1 (L1)", what);
+    if ((rc = loss_kind_check(what, a->loss_kind, a->loss_yuv, a->loss_chroma, a->img_height, a->img_width)))
+        return rc;
     if (!a->loss) return set_error(GSVC_ERR_ARG, "%s: null loss", what);
     const size_t need = gsvc_train_step_workspace_bytes(a->num_points, a->img_height, a->img_width);
     if (!a->train_workspace || a->train_workspace_bytes < need)
@@ -500,6 +500,8 @@ static int quant_step_enqueue(const gsvc_quant_train_args *a, const char *what) 
     T.img_height = a->img_height;
     T.img_width = a->img_width;
     T.loss_kind = a->loss_kind;
+    T.loss_yuv = a->loss_yuv;
+    T.loss_chroma = a->loss_chroma;
     T.frame_index = a->frame_index;
     T.adan_hparams = a->adan_hparams;
     T.adan_flags = det ? GSVC_TRAIN_DETERMINISTIC : 0;

@@ -42,7 +42,7 @@ namespace gsvc {
 constexpr int kT = kTilePix;  // threads = pixels = entries of one tile
 
 struct TrainTileArgs {
-    int tbx, img_w, img_h, ntiles, num_points, loss_l1;
+    int tbx, img_w, img_h, ntiles, num_points, loss_l1;  // loss_l1: the loss kind (0 L2, 1 L1, 2 Y/U/V)
     float norm;  // d loss / d pixel scale: float(2 / numel) for L2, 1.0f / numel for L1
     float4 *slab;  // read; a dense tile parks its sorted ids in its own slab
     const int *ovf;  // the slab's slots 256 .. kCarryCap - 1 as ids (frame.h FrameWs.ovf)
@@ -55,14 +55,15 @@ struct TrainTileArgs {
     const float *bg;
     const float *gt;  // [3, H, W]
     float *grad;      // [N, 16]: v_xy 0:2, v_conic 2:5, v_colors 5:8, v_opacity 8
-    float2 *err;      // [ntiles]: sum of squared, sum of absolute errors
+    float2 *err;      // [ntiles]: sum of squared, sum of absolute errors (loss_l1 == 2: of the
+                      // weighted squared Y/U/V block means, see yuv_w)
     // unused[]: the words of four retired A/B arguments.  The argument layout is
     // kept because the band kernel's code follows it: without these words the
     // deterministic carry instance spills 18 SGPRs instead of 8 (kernel resource
     // remarks; moving the live fields instead changed all four instances).
     int tgt16;        // band kernel: the targets as whole-tile 16-byte loads (img_w % 4 == 0 and
                       // gt 16-byte aligned: train_step_impl), else the 4-byte pair loads
-    int unused0[1];
+    int yuv_chroma;   // loss_l1 == 2: 0 4:2:0, 1 4:2:2, 2 4:4:4 (a retired argument's word)
     int grouped;      // band kernel forward: lane-group entry lists (GSVC_KNOB_TILE_NO_GROUPS = 1: off)
     int diag;         // GSVC_KNOB_TILE_ABLATE (timing experiments only; wrong results):
                       // bits 2 no backward, 4 no forward
@@ -80,7 +81,13 @@ struct TrainTileArgs {
     const int *det_off;
     float4 *det_part;
     long long det_cap;
-    int unused1[2];
+    // loss_l1 == 2 (band kernel): the weighted Y/U/V loss's constants
+    // (include/gsvc_amd.h), YuvConsts in the workspace, written on the stream
+    // before the tile kernel (yuv_consts_kernel) and read by scalar loads inside
+    // that branch only.  In the two retired words before cids: appended to this
+    // struct as 21 floats instead, every instance's register allocation
+    // changed and the L2 step's tile kernel took 0.4 us longer.
+    const struct YuvConsts *yuv;
     // GSVC_TRAIN_CARRY (band kernel): the tile's candidates are the splat ids
     // cids[tile][0, counts[tile]) -- a superset of its entries carried from
     // step to step (train_splat_kernel) -- and an entry is a candidate whose
@@ -97,6 +104,21 @@ struct TrainTileArgs {
     int *m_clear;
     unsigned *csorted;
 };
+static_assert(sizeof(TrainTileArgs) == 224, "the band kernel's code follows this layout (unused[])");
+
+// m: the RGB -> (Y, U, V) matrix M, rows Y, U, V; w[k] = w'_k = 3 w_k / sum w
+// (so that err.y / numel is the loss); g[k][c] = (2 / numel) w'_k M[k][c], the
+// gradient of that loss with respect to channel c per unit of plane k's block
+// mean -- each formed in double on the host and rounded to float once.
+struct YuvConsts {
+    float m[9], g[9], w[3];
+};
+
+// the constants into the workspace, from kernel arguments: no host buffer has
+// to outlive the call, and a capturing or busy stream orders it like any launch
+__global__ void yuv_consts_kernel(YuvConsts c, YuvConsts *dst) {
+    if (threadIdx.x == 0) *dst = c;
+}
 
 __device__ __forceinline__ float clamp_unit(float x) {
     // torch.clamp(x, 0, 1): NaN stays NaN
@@ -1147,7 +1169,8 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
     if (kStamp && tid == 0) st[2] = tstamp();
     __builtin_amdgcn_s_setprio(0);  // (the forward's priority ends here)
 
-    // 3. clamp, loss gradient (mse_loss backward: norm * (a - b); l1: norm * sgn),
+    // 3. clamp, loss gradient (mse_loss backward: norm * (a - b); l1: norm * sgn;
+    // loss_l1 == 2: the weighted Y/U/V loss, block means through yuv_g),
     // clamp backward (passes where 0 <= out <= 1), error sums; v_out planes
     {
         const float o[3][2] = {{ar.x, ar.y}, {ag.x, ag.y}, {ab.x, ab.y}};
@@ -1189,7 +1212,57 @@ __global__ __launch_bounds__(kBThreads, 8) void train_tile_band_kernel(TrainTile
         }
         // one branch on the loss kind (wave-uniform) around the six gradients: as a
         // select per value the L2 step paid for the six signs as well
-        if (A.loss_l1) {
+        if (A.loss_l1 == 2) {
+            // (constant address space: uniform reads of memory no one writes
+            // while this kernel runs become scalar loads)
+            const __attribute__((address_space(4))) YuvConsts &Y =
+                *(const __attribute__((address_space(4))) YuvConsts *)A.yuv;
+            // the weighted Y/U/V loss: per pixel e_k = sum_c M[k][c] d_c (a pixel
+            // outside the image: d = 0), Y per pixel, U and V as the mean over
+            // the chroma block -- 4:2:2 the lane's own pair, 4:2:0 that plus the
+            // pair of lane ^ 8, the block's other row (prow = 8 w + (lane >> 3)
+            // and bands start on even rows: the same wave, one row rotate by 8
+            // within the 16-lane row; a + b = b + a, so both rows hold the same
+            // bits).  The gradient is sum_k G[k][c] mean_k, and the tile's word 1
+            // sums w'_k mean_k^2 over its inside pixels, each with its own block's.
+            float eb[3][2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const bool inside = q < nin;
+                const float d0 = inside ? d[0][q] : 0.0f, d1 = inside ? d[1][q] : 0.0f,
+                            d2 = inside ? d[2][q] : 0.0f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    eb[k][q] = fmaf(Y.m[3 * k + 2], d2, fmaf(Y.m[3 * k + 1], d1, Y.m[3 * k] * d0));
+            }
+            if (A.yuv_chroma != 2) {
+                const bool rows2 = A.yuv_chroma == 0;
+#pragma unroll
+                for (int k = 1; k < 3; ++k) {
+                    float s = eb[k][0] + eb[k][1];
+                    if (rows2)
+                        s += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x128, 0xf, 0xf,
+                                                                        true));  // row_ror:8 = lane ^ 8
+                    s *= rows2 ? 0.25f : 0.5f;
+                    eb[k][0] = s;
+                    eb[k][1] = s;
+                }
+            }
+            float ye = 0.f;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                float pye = 0.f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) pye = fmaf(Y.w[k] * eb[k][q], eb[k][q], pye);
+                if (q < nin) ye += pye;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float g = fmaf(Y.g[6 + c], eb[2][q], fmaf(Y.g[3 + c], eb[1][q], Y.g[c] * eb[0][q]));
+                    v[c][q] = (q < nin && o[c][q] >= 0.0f && o[c][q] <= 1.0f) ? g : 0.0f;
+                }
+            }
+            ae = ye;  // word 1 of the tile's sums
+        } else if (A.loss_l1) {
 #pragma unroll
             for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -1828,6 +1901,7 @@ struct TrainWs {
     int *cids;
     unsigned *ccount, *csorted;  // csorted: TrainTileArgs.csorted, right after ccount
     uint2 *cbox, *chull;
+    YuvConsts *yuv;  // loss_kind 2's constants (TrainTileArgs.yuv)
     size_t bytes;
 };
 
@@ -1848,8 +1922,39 @@ static TrainWs train_ws(char *base, int n, int ntiles) {
     w.csorted = w.ccount ? w.ccount + nt : nullptr;
     w.cbox = (uint2 *)take(sizeof(uint2) * nn);
     w.chull = (uint2 *)take(sizeof(uint2) * nn);
+    w.yuv = (YuvConsts *)take(sizeof(YuvConsts));
     w.bytes = off;
     return w;
+}
+
+int loss_kind_check(const char *what, int loss_kind, const float *loss_yuv, int loss_chroma,
+                    unsigned img_height, unsigned img_width) {
+    if (loss_kind < 0 || loss_kind > 2)
+        return set_error(GSVC_ERR_ARG, "%s: loss_kind must be 0 (L2), 1 (L1) or 2 (weighted Y/U/V)", what);
+    if (loss_kind != 2) return GSVC_OK;
+    if (!loss_yuv)
+        return set_error(GSVC_ERR_ARG, "%s: loss_kind 2 needs loss_yuv (the matrix and weights)", what);
+    if (loss_chroma < 0 || loss_chroma > 2)
+        return set_error(GSVC_ERR_ARG, "%s: loss_chroma must be 0 (4:2:0), 1 (4:2:2) or 2 (4:4:4), got %d",
+                         what, loss_chroma);
+    if ((loss_chroma < 2 && img_width % 2) || (loss_chroma == 0 && img_height % 2))
+        return set_error(GSVC_ERR_ARG, "%s: a %ux%u image does not fit %s chroma blocks (needs an even "
+                         "width%s)", what, img_width, img_height, loss_chroma ? "4:2:2" : "4:2:0",
+                         loss_chroma ? "" : " and height");
+    double sum = 0.0;
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(loss_yuv[k]))
+            return set_error(GSVC_ERR_ARG, "%s: loss_yuv[%d] is not finite", what, k);
+    for (int k = 9; k < 12; ++k) {
+        if (loss_yuv[k] < 0.0f)
+            return set_error(GSVC_ERR_ARG, "%s: negative loss weight %g", what, (double)loss_yuv[k]);
+        sum += (double)loss_yuv[k];
+    }
+    if (!(sum > 0.0)) return set_error(GSVC_ERR_ARG, "%s: the loss weights sum to zero", what);
+    if (knob(GSVC_KNOB_TILE_WG256) == 1)
+        return set_error(GSVC_ERR_ARG, "%s: loss_kind 2 is not built into the 256-thread tile kernel "
+                         "(GSVC_KNOB_TILE_WG256)", what);
+    return GSVC_OK;
 }
 
 }  // namespace gsvc
@@ -1875,13 +1980,15 @@ static int train_step_impl(int num_points, float *xyz, float *cholesky,
                            const double *adan_hparams, int adan_flags, float *loss,
                            float *render_out, float *grads_out, void *workspace,
                            size_t workspace_bytes, void *stream, void *det_workspace,
-                           size_t det_workspace_bytes, long long det_capacity) {
+                           size_t det_workspace_bytes, long long det_capacity,
+                           const float *loss_yuv, int loss_chroma) {
     if (num_points < 0 || img_height == 0 || img_width == 0)
         return set_error(GSVC_ERR_ARG, "train_step_sum: bad sizes");
     if (!xyz || !cholesky || !features || !background || !gt || !loss || !adan_hparams)
         return set_error(GSVC_ERR_ARG, "train_step_sum: missing input");
-    if (loss_kind != 0 && loss_kind != 1)
-        return set_error(GSVC_ERR_ARG, "train_step_sum: loss_kind must be 0 (L2) or 1 (L1)");
+    if (const int rc = loss_kind_check("train_step_sum", loss_kind, loss_yuv, loss_chroma, img_height,
+                                       img_width))
+        return rc;
     if (rgb_w_trainable && !rgb_w)
         return set_error(GSVC_ERR_ARG, "train_step_sum: trainable rgb_w needs rgb_w");
     const bool update = grads_out == nullptr;
@@ -2015,6 +2122,23 @@ static int train_step_impl(int num_points, float *xyz, float *cholesky,
     T.num_points = num_points;
     T.loss_l1 = loss_kind;
     T.norm = loss_kind ? 1.0f / (float)count : (float)(2.0 / count);
+    if (loss_kind == 2 && !tiled) {  // (TILED: the previous call's tile kernel read its own)
+        // w'_k = 3 w_k / sum w; G[k][c] = (2 / numel) w'_k M[k][c]: in double, rounded once
+        YuvConsts C;
+        const double wsum = (double)loss_yuv[9] + (double)loss_yuv[10] + (double)loss_yuv[11];
+        for (int k = 0; k < 3; ++k) {
+            const double wk = 3.0 * (double)loss_yuv[9 + k] / wsum;
+            C.w[k] = (float)wk;
+            for (int c = 0; c < 3; ++c) {
+                C.m[3 * k + c] = loss_yuv[3 * k + c];
+                C.g[3 * k + c] = (float)((2.0 / count) * wk * (double)loss_yuv[3 * k + c]);
+            }
+        }
+        hipLaunchKernelGGL(yuv_consts_kernel, dim3(1), dim3(64), 0, s, C, w.yuv);
+        if (const int r = check_launch("train_step_sum: loss constants")) return r;
+    }
+    T.yuv = w.yuv;
+    T.yuv_chroma = loss_kind == 2 ? loss_chroma : 0;
     T.slab = w.f.slab;
     T.ovf = w.f.ovf;
     T.xys = w.f.xys;
@@ -2185,10 +2309,12 @@ extern "C" int gsvc_train_step_sum(int num_points, float *xyz, float *cholesky,
                                    const double *adan_hparams, int adan_flags, float *loss,
                                    float *render_out, float *grads_out, void *workspace,
                                    size_t workspace_bytes, void *stream) {
+    if (loss_kind != 0 && loss_kind != 1)
+        return set_error(GSVC_ERR_ARG, "train_step_sum: loss_kind must be 0 (L2) or 1 (L1)");
     return train_step_impl(num_points, xyz, cholesky, cholesky_bound, features, rgb_w,
                            rgb_w_trainable, background, gt, img_height, img_width, loss_kind,
                            frame_index, adan_state, adan_hparams, adan_flags, loss, render_out,
-                           grads_out, workspace, workspace_bytes, stream, nullptr, 0, 0);
+                           grads_out, workspace, workspace_bytes, stream, nullptr, 0, 0, nullptr, 0);
 }
 
 extern "C" int gsvc_train_step_sum_args(const gsvc_train_step_args *a) {
@@ -2198,5 +2324,5 @@ extern "C" int gsvc_train_step_sum_args(const gsvc_train_step_args *a) {
                            a->img_width, a->loss_kind, a->frame_index, a->adan_state,
                            a->adan_hparams, a->adan_flags, a->loss, a->render_out, a->grads_out,
                            a->workspace, a->workspace_bytes, a->stream, a->det_workspace,
-                           a->det_workspace_bytes, a->det_capacity);
+                           a->det_workspace_bytes, a->det_capacity, a->loss_yuv, a->loss_chroma);
 }

@@ -25,15 +25,65 @@ from .render import BoundRender, render_frame_sum
 from .train import LOSS_KIND, BoundStep
 
 
-def loss_fn(pred, target, loss_type="L2", lambda_value=0.7):
+def _default_yuv_loss():
+    from .video import YuvLoss  # (video imports this module)
+    return YuvLoss()
+
+
+def yuv_plane_mse(pred, target, spec):
+    """The three plane errors of the weighted Y/U/V loss (``spec``: a
+    gsvc_amd.video.YuvLoss) as a tensor [3] in the inputs' dtype: with d =
+    pred - target ([3,H,W] or [1,3,H,W]) and e = M d per pixel, mse_Y is the
+    mean of e_Y^2 over the pixels, mse_U and mse_V the means over the chroma
+    blocks (2x2 at 4:2:0, 2x1 at 4:2:2, 1x1 at 4:4:4, aligned to even
+    coordinates) of the squared block mean.  Plain differentiable torch, CPU
+    or CUDA tensors.  Not part of the reference."""
+    if pred.dim() == 4:
+        if pred.shape[0] != 1:
+            raise ValueError("yuv_plane_mse takes one image: [3,H,W] or [1,3,H,W]")
+        pred = pred[0]
+    if target.dim() == 4:
+        target = target[0]
+    if pred.dim() != 3 or pred.shape[0] != 3 or target.shape != pred.shape:
+        raise ValueError(f"yuv_plane_mse takes [3,H,W] images of one size, not {tuple(pred.shape)} "
+                         f"and {tuple(target.shape)}")
+    H, W = pred.shape[1:]
+    spec.check_size(H, W)
+    M = torch.as_tensor(spec.M, dtype=pred.dtype, device=pred.device)
+    e = torch.einsum("kc,chw->khw", M, pred - target.detach())
+    code = spec.chroma_code
+    by, bx = (2 if code == 0 else 1), (1 if code == 2 else 2)
+    c = e[1:]
+    if by * bx > 1:
+        c = c.reshape(2, H // by, by, W // bx, bx).mean(dim=(2, 4))
+    return torch.cat([(e[0] * e[0]).mean().reshape(1), (c * c).mean(dim=(1, 2))])
+
+
+def yuv_loss(pred, target, spec=None):
+    """The weighted Y/U/V loss sum_k w_k mse_k / sum_k w_k of ``yuv_plane_mse``
+    (``spec`` None: ``YuvLoss()``, 6:1:1 at the legacy format's 4:2:0): the op
+    path's statement of what the fused step's ``loss_type="YUV"`` computes."""
+    spec = spec or _default_yuv_loss()
+    w = torch.as_tensor(spec.weights, dtype=pred.dtype, device=pred.device)
+    return (w * yuv_plane_mse(pred, target, spec)).sum() / w.sum()
+
+
+_yuv_loss = yuv_loss  # (loss_fn's keyword has the function's name)
+
+
+def loss_fn(pred, target, loss_type="L2", lambda_value=0.7, yuv_loss=None):
     """utils.py:21-41.  The SSIM terms are gsvc_amd.msssim (pytorch_msssim's
     ssim / ms_ssim on the gfx950 kernels, CUDA tensors only); as in the
     reference they need 4-d inputs, so train_iter's squeezed [3,H,W] images
     raise for them there (GaussianSplats_Represent.py:194) and pre_train_iter's
-    NCHW ones (:213) work."""
+    NCHW ones (:213) work.  "YUV" (not part of the reference) is the weighted
+    Y/U/V loss of ``yuv_loss`` (a YuvLoss; None: ``YuvLoss()``); lambda_value
+    does not enter it."""
     target = target.detach()
     pred = pred.float()
     target = target.float()
+    if loss_type == "YUV":
+        return _yuv_loss(pred, target, yuv_loss)
     if loss_type == "L2":
         return F.mse_loss(pred, target)
     if loss_type == "L1":
@@ -62,6 +112,11 @@ class GaussianVideoFrame(nn.Module):
     def __init__(self, loss_type="L2", **kwargs):
         super().__init__()
         self.loss_type = loss_type
+        # loss_type "YUV": the weighted Y/U/V loss's spec (video.YuvLoss; None: YuvLoss())
+        self.yuv_loss = kwargs.get("yuv_loss")
+        if loss_type == "YUV":
+            self.yuv_loss = self.yuv_loss or _default_yuv_loss()
+            self.yuv_loss.check_size(kwargs["H"], kwargs["W"])
         self.init_num_points = kwargs["num_points"]
         self.max_num_points = kwargs["max_num_points"]
         self.densification_interval = kwargs["densification_interval"]
@@ -244,7 +299,7 @@ class GaussianVideoFrame(nn.Module):
 
     def _fused_train_params(self, gt_image):
         """(rgb_W trainable?) when this iteration can run as one fused step
-        (train.py): L2 / L1 loss, Adan without gradient clipping, the model's
+        (train.py): L2 / L1 / YUV loss, Adan without gradient clipping, the model's
         own parameters in one group, no gradients pending; else None.  The
         configuration checks are cached against the objects they looked at
         (optimizer, its group list, the parameters); per call only the pending
@@ -330,9 +385,10 @@ class GaussianVideoFrame(nn.Module):
         B = self._buffers
         bound = (xyz, chol, feat, rgbw, B["cholesky_bound"], B["background"], *state)
         bs = self._bound_step
-        if bs is None or bs.rgbw_train != int(rgbw_train) or not bs.matches(bound):
+        if (bs is None or bs.rgbw_train != int(rgbw_train) or not bs.matches(bound)
+                or bs.loss_type != self.loss_type or bs.yuv_loss is not self.yuv_loss):
             bs = self._bound_step = BoundStep(*bound[:4], rgbw_train, *bound[4:6], self.H, self.W,
-                                              self.loss_type, state)
+                                              self.loss_type, state, yuv_loss=self.yuv_loss)
         bs.launch(gt, hparams, flags)
         # the step ran (keeps StepLR's call-order check quiet; the scheduler may
         # hold the optimizer from before update_optimizer, as in the reference).
@@ -346,8 +402,9 @@ class GaussianVideoFrame(nn.Module):
         # made while the kernels run: after the wait only its value is stored
         loss = torch.empty(())
         loss_np = loss.numpy()
+        # (mse, l1), or with the YUV loss (rgb mse, that loss)
         mse, l1 = bs.result()  # the reference's PSNR .item(): one stream wait
-        loss_np[...] = l1 if self.loss_type == "L1" else mse
+        loss_np[...] = mse if self.loss_type == "L2" else l1
         psnr = 10 * math.log10(1.0 / mse)
         return loss, psnr
 
@@ -368,7 +425,8 @@ class GaussianVideoFrame(nn.Module):
             # its step count.  Forward only (the same image bits and loss).
             with torch.no_grad():
                 image = self.forward()["render"]
-                loss = loss_fn(image.squeeze(0), gt_image.squeeze(0), self.loss_type, lambda_value=0)
+                loss = loss_fn(image.squeeze(0), gt_image.squeeze(0), self.loss_type, lambda_value=0,
+                               yuv_loss=self.yuv_loss)
                 psnr = 10 * math.log10(1.0 / F.mse_loss(image, gt_image).item())
             if (iter == 1 or iter % self.densification_interval == 0) and self.isdensity:
                 self.adaptive_control(iter)
@@ -380,7 +438,8 @@ class GaussianVideoFrame(nn.Module):
             return loss, psnr
         render_pkg = self.forward()
         image = render_pkg["render"]
-        loss = loss_fn(image.squeeze(0), gt_image.squeeze(0), self.loss_type, lambda_value=0)
+        loss = loss_fn(image.squeeze(0), gt_image.squeeze(0), self.loss_type, lambda_value=0,
+                               yuv_loss=self.yuv_loss)
         loss.backward()
         with torch.no_grad():
             mse_loss = F.mse_loss(image, gt_image)
@@ -398,7 +457,8 @@ class GaussianVideoFrame(nn.Module):
         """GaussianSplats_Represent.py:175-188: train_iter returning the render."""
         render_pkg = self.forward()
         image = render_pkg["render"]
-        loss = loss_fn(image.squeeze(0), gt_image.squeeze(0), self.loss_type, lambda_value=0)
+        loss = loss_fn(image.squeeze(0), gt_image.squeeze(0), self.loss_type, lambda_value=0,
+                               yuv_loss=self.yuv_loss)
         loss.backward()
         if (iter == 1 or iter % self.densification_interval == 0) and self.isdensity:
             self.adaptive_control(iter)
@@ -412,13 +472,13 @@ class GaussianVideoFrame(nn.Module):
     def pre_train_iter(self, gt_image):
         """GaussianSplats_Represent.py:210-222 (the K-frame detector's step): no
         pruning or densification, the loss on the NCHW images with lambda 0.7.
-        L2 / L1 take the fused step (lambda does not enter them)."""
+        L2 / L1 / YUV take the fused step (lambda does not enter them)."""
         rgbw_train = self._fused_train_params(gt_image)
         if rgbw_train is not None:
             return self._train_iter_fused(gt_image, rgbw_train)
         render_pkg = self.forward()
         image = render_pkg["render"]
-        loss = loss_fn(image, gt_image, self.loss_type, lambda_value=0.7)
+        loss = loss_fn(image, gt_image, self.loss_type, lambda_value=0.7, yuv_loss=self.yuv_loss)
         loss.backward()
         with torch.no_grad():
             mse_loss = F.mse_loss(image, gt_image)
@@ -431,14 +491,16 @@ class GaussianVideoFrame(nn.Module):
 
 def make_frame_model(H, W, num_points, device, seed=None, lr=1e-3, isremoval=False,
                      isdensity=False, removal_rate=0.1, max_num_points=None,
-                     densification_interval=100, fused_train=None, fused_render=None):
+                     densification_interval=100, fused_train=None, fused_render=None,
+                     loss_type="L2", yuv_loss=None):
     """Construct like SimpleTrainer2d does (train_video_Represent.py:51-55).
+    loss_type "YUV" with ``yuv_loss`` (a video.YuvLoss): the weighted Y/U/V loss.
     fused_train / fused_render False: train_iter / forward() take GSVC's own op
     sequence through the gsplat operators (the unchanged-caller path)."""
     if seed is not None:
         torch.manual_seed(seed)
     model = GaussianVideoFrame(
-        loss_type="L2", opt_type="adan", num_points=num_points,
+        loss_type=loss_type, yuv_loss=yuv_loss, opt_type="adan", num_points=num_points,
         max_num_points=max_num_points or num_points, densification_interval=densification_interval,
         iterations=30000, H=H, W=W, BLOCK_H=16, BLOCK_W=16, device=device, lr=lr, quantize=False,
         removal_rate=removal_rate, isdensity=isdensity, isremoval=isremoval,

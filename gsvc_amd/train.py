@@ -2,7 +2,8 @@
 
 ``train_step_sum`` runs what ``GaussianVideo_frame.train_iter``
 (GaussianSplats_Represent.py:191-207) does between ``forward()`` and
-``scheduler.step()`` for the L2 / L1 losses and Adan -- forward, clamp, loss,
+``scheduler.step()`` for the L2 / L1 losses (and the weighted Y/U/V loss of
+video.YuvLoss, which is not the reference's) and Adan -- forward, clamp, loss,
 backward through the rasterizer, the projection and the activations, and the
 Adan update of every parameter -- as three gfx950 kernels
 (gsvc_amd/csrc/train.hip, ``gsvc_train_step_sum``).  ``GaussianVideoFrame``
@@ -22,7 +23,7 @@ from torch import Tensor
 
 from . import _lib as L
 
-LOSS_KIND = {"L2": 0, "L1": 1}
+LOSS_KIND = {"L2": 0, "L1": 1, "YUV": 2}  # include/gsvc_amd.h loss_kind
 TRAIN_LOSS_SEQ = 0x100  # include/gsvc_amd.h GSVC_TRAIN_LOSS_SEQ
 TRAIN_ORDER = 0x200  # GSVC_TRAIN_ORDER
 TRAIN_ORDER_REFRESH = 0x400  # GSVC_TRAIN_ORDER_REFRESH
@@ -210,7 +211,27 @@ class _StepArgs(ctypes.Structure):
                 ("render_out", ctypes.c_void_p), ("grads_out", ctypes.c_void_p),
                 ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
                 ("stream", ctypes.c_void_p), ("det_workspace", ctypes.c_void_p),
-                ("det_workspace_bytes", ctypes.c_size_t), ("det_capacity", ctypes.c_longlong)]
+                ("det_workspace_bytes", ctypes.c_size_t), ("det_capacity", ctypes.c_longlong),
+                ("loss_yuv", ctypes.c_void_p), ("loss_chroma", ctypes.c_int)]
+
+
+def loss_args(a, loss_type: str, yuv_loss, H: int, W: int):
+    """Set ``loss_kind`` and, for "YUV", ``loss_yuv`` / ``loss_chroma`` of the
+    argument struct ``a`` (_StepArgs or compress._QuantStepArgs) from
+    ``yuv_loss`` (a video.YuvLoss; None: ``YuvLoss()``).  Returns the host
+    words ``loss_yuv`` points to: the caller keeps them alive with ``a``."""
+    if loss_type not in LOSS_KIND:
+        raise ValueError(f"fused training supports the L2, L1 and YUV losses, not {loss_type!r}")
+    a.loss_kind = LOSS_KIND[loss_type]
+    if loss_type != "YUV":
+        a.loss_yuv, a.loss_chroma = None, 0
+        return None
+    if yuv_loss is None:
+        from .video import YuvLoss
+        yuv_loss = YuvLoss()
+    words = yuv_loss.words()  # (the library checks the size against the chroma)
+    a.loss_yuv, a.loss_chroma = ctypes.addressof(words), yuv_loss.chroma_code
+    return words
 
 
 class BoundStep:
@@ -222,8 +243,9 @@ class BoundStep:
     through their storage (as ``p.data`` would be)."""
 
     def __init__(self, xyz, cholesky, features, rgb_w, rgb_w_trainable, cholesky_bound,
-                 background, H, W, loss_type, adan_state):
+                 background, H, W, loss_type, adan_state, *, yuv_loss=None):
         n = xyz.shape[0]
+        self.loss_type, self.yuv_loss = loss_type, yuv_loss  # (the owner rebuilds when either changes)
         self.tensors = (xyz, cholesky, features, rgb_w, cholesky_bound, background, *adan_state)
         self.ids = tuple(map(id, self.tensors))  # the objects stay alive via self.tensors
         self.n, self.H, self.W = n, int(H), int(W)
@@ -248,7 +270,7 @@ class BoundStep:
         a.rgb_w_trainable = self.rgbw_train
         a.background = _f32_ptr(background, "background", 3)
         a.img_height, a.img_width = self.H, self.W
-        a.loss_kind = LOSS_KIND[loss_type]
+        self.loss_words = loss_args(a, loss_type, yuv_loss, self.H, self.W)
         a.adan_state = ctypes.addressof(self.state)
         a.adan_hparams = ctypes.addressof(self.hp)
         self.args_ref = ctypes.byref(a)
@@ -392,8 +414,9 @@ class BoundStep:
             raise RuntimeError(f"gsvc_train_step_sum failed (status {rc}): {msg}")
 
     def result(self):
-        """(mean squared error, mean absolute error) of the last launched step:
-        waits for its sequence word (the reference's PSNR ``.item()``); after
+        """(mean squared error, mean absolute error) of the last launched step
+        -- with the YUV loss (rgb mean squared error, yuv_loss): the PSNR is still
+        the RGB one -- waits for its sequence word (the reference's PSNR ``.item()``); after
         50 ms of spinning, for the whole stream, which reports a failed kernel."""
         L.call("gsvc_wait_host_seq", self.host + 8, self.seq, self.stream, 50000)
         if self.det:
@@ -426,9 +449,11 @@ def train_step_sum(xyz: Tensor, cholesky: Tensor, features: Tensor, rgb_w: Optio
                    gt: Tensor, img_height: int, img_width: int, loss_type: str = "L2",
                    adan_state: Sequence[Optional[Tensor]] = (), adan_hparams: Sequence[float] = (),
                    adan_flags: int = 0, render_out: Optional[Tensor] = None,
-                   grads_out: Optional[Tensor] = None) -> Tensor:
+                   grads_out: Optional[Tensor] = None, *, yuv_loss=None) -> Tensor:
     """One fused training step; returns a device tensor [2] = (mean squared
-    error, mean absolute error) of clamp(render) against ``gt``.
+    error, mean absolute error) of clamp(render) against ``gt``.  With
+    ``loss_type="YUV"`` the step descends the weighted Y/U/V loss of
+    ``yuv_loss`` (a video.YuvLoss; None: ``YuvLoss()``) and word 1 is that loss.
 
     Parameters are updated in place (xyz [N,2], cholesky [N,3], features
     [N,3], and rgb_w [N,1] when ``rgb_w_trainable``) with Adan; ``adan_state``
@@ -438,7 +463,7 @@ def train_step_sum(xyz: Tensor, cholesky: Tensor, features: Tensor, rgb_w: Optio
     """
     H, W = int(img_height), int(img_width)
     if loss_type not in LOSS_KIND:
-        raise ValueError(f"fused training supports the L2 and L1 losses, not {loss_type!r}")
+        raise ValueError(f"fused training supports the L2, L1 and YUV losses, not {loss_type!r}")
     n = xyz.shape[0]
     dev = xyz.device
     p_xyz = _f32_ptr(xyz, "xyz", 2 * n)
@@ -468,7 +493,8 @@ def train_step_sum(xyz: Tensor, cholesky: Tensor, features: Tensor, rgb_w: Optio
     a.num_points, a.xyz, a.cholesky, a.cholesky_bound = n, p_xyz, p_chol, p_bound
     a.features, a.rgb_w, a.rgb_w_trainable = p_feat, p_rgbw, 1 if rgb_w_trainable else 0
     a.background, a.gt, a.img_height, a.img_width = p_bg, p_gt, H, W
-    a.loss_kind, a.frame_index = LOSS_KIND[loss_type], ws.frame
+    a.frame_index = ws.frame
+    loss_words = loss_args(a, loss_type, yuv_loss, H, W)  # noqa: F841 (alive over the call)
     a.adan_state, a.adan_hparams = ctypes.addressof(state), ctypes.addressof(hp)
     flags = int(adan_flags)
     if torch.are_deterministic_algorithms_enabled():

@@ -278,6 +278,70 @@ def format_of_arguments(args, base: Optional[YuvFormat] = None) -> Optional[YuvF
                        for f, g in zip(("bit_depth", "matrix", "full_range", "chroma", "layout"), given)))
 
 
+@dataclasses.dataclass(frozen=True)
+class YuvLoss:
+    """The weighted Y/U/V training loss (``loss_type="YUV"``):
+    with d = clamp(render, 0, 1) - target, e_k = sum_c M[k][c] d_c per pixel,
+    Y per pixel and U, V averaged over ``fmt``'s chroma block (2x2 at 4:2:0,
+    2x1 at 4:2:2, 1x1 at 4:4:4),
+
+        L = sum_k w_k mse_k / sum_k w_k,    mse_k = mean over blocks of (block mean of e_k)^2,
+
+    so 10 log10(1 / mse_k) is plane k's PSNR before sample rounding, in units
+    of the format's full code range.  M is the matrix the output conversion
+    computes with, ``fmt.conversion_table()[9:18] / 2**20`` (rows Y, U, V):
+    only ``fmt.matrix``, ``fmt.full_range`` and ``fmt.chroma`` matter (the depth
+    enters through the table's rounding, the layout not at all).  ``matrix``
+    overrides M with an explicit 3x3 (another colour space).  ``weights`` are
+    (w_Y, w_U, w_V), non-negative with a positive sum; the default is the
+    usual 6:1:1."""
+    fmt: YuvFormat = YuvFormat()
+    weights: tuple = (6.0, 1.0, 1.0)
+    matrix: Optional[tuple] = None
+
+    def __post_init__(self):
+        if not isinstance(self.fmt, YuvFormat):
+            raise TypeError(f"fmt is a YuvFormat, not {type(self.fmt).__name__}")
+        w = tuple(float(x) for x in self.weights)
+        if len(w) != 3 or not all(math.isfinite(x) and x >= 0.0 for x in w) or not sum(w) > 0.0:
+            raise ValueError(f"weights are three non-negative numbers with a positive sum, not {self.weights!r}")
+        object.__setattr__(self, "weights", w)
+        if self.matrix is not None:
+            m = np.asarray(self.matrix, dtype=np.float64)
+            if m.shape != (3, 3) or not np.isfinite(m).all():
+                raise ValueError("matrix is a finite 3x3 (rows Y, U, V over R, G, B)")
+            object.__setattr__(self, "matrix", tuple(tuple(float(x) for x in row) for row in m))
+
+    @property
+    def M(self) -> np.ndarray:
+        """The 3x3 RGB -> (Y, U, V) matrix as float64, rows Y, U, V."""
+        if self.matrix is not None:
+            return np.array(self.matrix, dtype=np.float64)
+        return np.array(self.fmt.conversion_table()[9:18], dtype=np.float64).reshape(3, 3) / 1048576.0
+
+    @property
+    def chroma_code(self) -> int:
+        """0: 4:2:0, 1: 4:2:2, 2: 4:4:4 (the container's chroma codes)."""
+        return _CHROMAS.index(self.fmt.chroma)
+
+    def check_size(self, height: int, width: int) -> None:
+        self.fmt.check_size(height, width)
+
+    def words(self):
+        """include/gsvc_amd.h ``loss_yuv``: M row-major, then the weights, as 12 floats."""
+        return (ctypes.c_float * 12)(*self.M.reshape(-1).tolist(), *self.weights)
+
+
+def parse_loss_weights(text: Optional[str]):
+    """``--loss_weights WY,WU,WV`` -> a tuple of three floats (None: 6, 1, 1)."""
+    if text is None:
+        return (6.0, 1.0, 1.0)
+    parts = str(text).split(",")
+    if len(parts) != 3:
+        raise ValueError(f"--loss_weights takes WY,WU,WV, not {text!r}")
+    return tuple(float(p) for p in parts)
+
+
 def _sample_bytes_of(t: torch.Tensor, fmt: YuvFormat, count: int, what: str) -> torch.Tensor:
     """``t`` (uint8 bytes, or int16 samples of a 16-bit format) as a flat uint8
     tensor of ``count`` bytes."""
@@ -634,7 +698,7 @@ class FrameTrainer:
     def __init__(self, image: torch.Tensor, frame_num: int, loss_type: str = "L2",
                  num_points: int = 2000, max_num_points: int = 2000, iterations: int = 30000,
                  lr: float = 1e-3, densification_interval: int = 100, trained_model=None,
-                 isdensity=False, isremoval=True, removal_rate=0.25, early_stop=True):
+                 isdensity=False, isremoval=True, removal_rate=0.25, early_stop=True, yuv_loss=None):
         self.device = image.device
         self.early_stop = early_stop  # False: every frame trains for ``iterations``
         self.gt_image = image
@@ -643,7 +707,7 @@ class FrameTrainer:
         self.isdensity, self.isremoval = isdensity, isremoval
         self.H, self.W = image.shape[2], image.shape[3]
         self.model = GaussianVideoFrame(
-            loss_type=loss_type, opt_type="adan", num_points=num_points,
+            loss_type=loss_type, yuv_loss=yuv_loss, opt_type="adan", num_points=num_points,
             max_num_points=max_num_points, densification_interval=densification_interval,
             iterations=iterations, H=self.H, W=self.W, BLOCK_H=16, BLOCK_W=16, device=self.device,
             lr=lr, quantize=False, removal_rate=removal_rate, isdensity=isdensity,
@@ -724,7 +788,8 @@ def _dist():
 
 
 def detect_k_frames(frame_fn, num_frames: int, rank: int, world: int, loss_type: str, lr: float,
-                    probe_points=5000, scratch_iters=500, probe_iters=100, seed: int = 1) -> List[int]:
+                    probe_points=5000, scratch_iters=500, probe_iters=100, seed: int = 1,
+                    yuv_loss=None) -> List[int]:
     """train_video_Represent.py:318-355 with frames split over ranks: rank r
     probes a contiguous range and recomputes the scratch model of the frame
     before its range (one-frame halo); the normalised loss list is gathered
@@ -732,20 +797,21 @@ def detect_k_frames(frame_fn, num_frames: int, rank: int, world: int, loss_type:
     lo, hi = (num_frames * rank) // world, (num_frames * (rank + 1)) // world
     losses: Dict[int, float] = {}
     prev = None
+    ykw = {} if yuv_loss is None else {"yuv_loss": yuv_loss}
     for i in range(max(lo - 1, 0), hi):
         img = frame_fn(i)
         # seeded by frame, not by rank: the halo frame's scratch model is the one
         # its owner trains, and the list does not depend on the world size
         torch.manual_seed(seed + i)
         k = FrameTrainer(img, i + 1, loss_type, probe_points, probe_points, scratch_iters, lr,
-                         isdensity=False, isremoval=False)
+                         isdensity=False, isremoval=False, **ykw)
         gm, loss_k = k.pre_train()
         if i >= lo:
             if i == 0:
                 losses[i] = 0.0
             else:
                 p = FrameTrainer(img, i + 1, loss_type, probe_points, probe_points, probe_iters, lr,
-                                 trained_model=prev, isdensity=False, isremoval=False)
+                                 trained_model=prev, isdensity=False, isremoval=False, **ykw)
                 _, loss_p = p.pre_train()
                 losses[i] = loss_p - loss_k
         prev = gm
@@ -777,6 +843,8 @@ def train_video(frame_fn, num_frames: int, k_frames: Sequence[int], args, rank: 
     per = {k: [] for k in ("psnr", "ms_ssim", "training_time", "eval_time", "eval_fps",
                            "num_gaussians")}
     log, models = [], {}
+    # (the spec only with --loss_type YUV: a caller's own trainer class keeps its signature)
+    ykw = {"yuv_loss": args.yuv_loss} if getattr(args, "yuv_loss", None) is not None else {}
     for start, end in mine:
         gmodel, npts = None, args.num_points
         for f in range(start, end):  # 1-based frame numbers
@@ -788,13 +856,13 @@ def train_video(frame_fn, num_frames: int, k_frames: Sequence[int], args, rank: 
                                   args.iterations, args.lr, args.densification_interval,
                                   isdensity=False, isremoval=args.is_rm,
                                   removal_rate=args.removal_rate,
-                                  early_stop=not getattr(args, "no_early_stop", False))
+                                  early_stop=not getattr(args, "no_early_stop", False), **ykw)
             else:  # a P-frame: from the previous frame's model
                 tr = FrameTrainer(img, f, args.loss_type, npts, args.num_points, args.iterations,
                                   args.lr, args.densification_interval, trained_model=gmodel,
                                   isdensity=args.is_ad, isremoval=False,
                                   removal_rate=args.removal_rate,
-                                  early_stop=not getattr(args, "no_early_stop", False))
+                                  early_stop=not getattr(args, "no_early_stop", False), **ykw)
             r = tr.train()
             gmodel, npts = r.pop("model"), r["num_gaussians"]
             models[f"frame_{f}"] = {k: v.cpu() for k, v in gmodel.items()}
@@ -828,7 +896,12 @@ def parse_args(argv=None):
     ap.add_argument("--iterations", type=int, default=30000)
     ap.add_argument("--densification_interval", type=int, default=100)
     ap.add_argument("--num_points", type=int, default=10000)
-    ap.add_argument("--loss_type", type=str, default="L2")
+    ap.add_argument("--loss_type", type=str, default="L2",
+                    help="L2, L1, the reference's SSIM / Fusion losses, or YUV: the weighted "
+                         "Y/U/V loss with chroma subsampled as --chroma / --pix_fmt say, in the "
+                         "colour space of --matrix / --full_range (fused step, like L2 / L1)")
+    ap.add_argument("--loss_weights", type=str, default=None, metavar="WY,WU,WV",
+                    help="plane weights of --loss_type YUV (default 6,1,1)")
     ap.add_argument("--seed", type=float, default=1)
     ap.add_argument("--removal_rate", type=float, default=0.1)
     ap.add_argument("--lr", type=float, default=1e-3)
@@ -841,7 +914,24 @@ def parse_args(argv=None):
     ap.add_argument("--ranks_per_gpu", type=int, default=1,
                     help="ranks sharing one GPU (each trains its own GOPs on its own stream; "
                          "> 1 uses gloo for the metric collectives, RCCL takes one rank per GPU)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    args.yuv_loss = yuv_loss_of_arguments(args, ap)
+    return args
+
+
+def yuv_loss_of_arguments(args, parser=None):
+    """The YuvLoss of --loss_type YUV, --loss_weights and the format options
+    (None for another loss type); a bad combination is a usage error."""
+    try:
+        if args.loss_type != "YUV":
+            if getattr(args, "loss_weights", None) is not None:
+                raise ValueError("--loss_weights goes with --loss_type YUV")
+            return None
+        return YuvLoss(format_of_arguments(args) or YuvFormat(), parse_loss_weights(args.loss_weights))
+    except ValueError as e:
+        if parser is None:
+            raise
+        parser.error(str(e))
 
 
 def rank_device(local: int, ranks_per_gpu: int, use_cuda: bool):
@@ -905,7 +995,9 @@ def main(argv=None):
         k_frames, source = [int(x) for x in kfile.read_text().split()], "file"
     else:
         k_frames, source = detect_k_frames(frame_fn, num_frames, rank, world, args.loss_type,
-                                           args.lr, seed=int(args.seed)), "detected"
+                                           args.lr, seed=int(args.seed),
+                                           **({} if args.yuv_loss is None else {"yuv_loss": args.yuv_loss})
+                                           ), "detected"
     # too few GOPs for the ranks: K-frames forced at equal-frame shard
     # boundaries
     if len(gops(k_frames, num_frames)) < world:

@@ -454,7 +454,19 @@ int gsvc_render_frame_sum_ex(int num_points, const float *xyz, int xyz_tanh,
  * gradients go to grads_out [N,9] = {d_xyz 2, d_cholesky 3, d_features 3,
  * d_rgb_w 1}.  Workspace: gsvc_train_step_workspace_bytes; its first
  * gsvc_render_frame_zeroed_bytes(H, W) bytes zero before the first call (every
- * call leaves them zero); frame_index alternates parity between calls. */
+ * call leaves them zero); frame_index alternates parity between calls.
+ *
+ * Weighted Y/U/V loss (loss_kind 2, gsvc_train_step_sum_args only; not part of
+ * the reference): with x = clamp(render, 0, 1), d = x - gt, the 3x3
+ * RGB -> (Y, U, V) matrix M and weights w of ``loss_yuv``, e_k = sum_c
+ * M[k][c] d_c per pixel, Y per pixel and U, V averaged over the chroma block
+ * of ``loss_chroma`` (2x2 at 4:2:0, 2x1 at 4:2:2, 1x1 at 4:4:4, aligned to
+ * even coordinates), the loss is
+ *   L = sum_k w_k mse_k / sum_k w_k,  mse_k = mean over blocks of (block mean e_k)^2,
+ * and its gradient passes the clamp where 0 <= render <= 1.  loss[0] stays
+ * the RGB mean squared error (the PSNR's), loss[1] <- L.  Weights are finite,
+ * non-negative, with a positive sum; 4:2:0 needs even img_height and
+ * img_width, 4:2:2 an even img_width (GSVC_ERR_ARG otherwise). */
 #define GSVC_TRAIN_LOSS_SEQ 0x100
 /* Splat order (speed only; the same results): GSVC_TRAIN_ORDER projects the
  * splats in the order an earlier GSVC_TRAIN_ORDER_REFRESH call of the same
@@ -560,6 +572,9 @@ typedef struct gsvc_train_step_args {
     void *det_workspace;
     size_t det_workspace_bytes;
     long long det_capacity;
+    /* loss_kind 2 only (else NULL / 0; see "Weighted Y/U/V loss" above) */
+    const float *loss_yuv; /* host float[12]: M row-major (rows Y, U, V), then w_Y, w_U, w_V */
+    int loss_chroma;       /* 0: 4:2:0, 1: 4:2:2, 2: 4:4:4 (the container's chroma codes) */
 } gsvc_train_step_args;
 int gsvc_train_step_sum_args(const gsvc_train_step_args *args);
 
@@ -1075,7 +1090,10 @@ int gsvc_encode_stream(int num_frames, const int *num_points, const unsigned cha
  *      and loss[0..3] = {mean squared error, mean absolute error, commitment
  *      sum of stage 0, of stage 1} (device or pinned host memory; read it
  *      after gsvc_stream_sync).  The step's loss is loss[loss_kind] +
- *      commitment_weight * (loss[2] + loss[3]) / (3 N).
+ *      commitment_weight * (loss[2] + loss[3]) / (3 N); with loss_kind 2
+ *      (the weighted Y/U/V loss of gsvc_train_step_sum_args, from loss_yuv
+ *      and loss_chroma) loss[1] holds that loss and takes loss[loss_kind]'s
+ *      place.
  * No float atomics anywhere in 1, 3 and 4: equal inputs give equal bits (step
  * 2 with GSVC_TRAIN_DETERMINISTIC in ``flags``, which needs det_workspace).
  * adan_state: host array of 20 device pointers, per parameter (xyz, cholesky,
@@ -1114,6 +1132,9 @@ typedef struct gsvc_quant_train_args {
     size_t det_workspace_bytes;
     long long det_capacity;
     void *stream;
+    /* loss_kind 2 only (else NULL / 0): gsvc_train_step_args' fields of the same names */
+    const float *loss_yuv;
+    int loss_chroma;
 } gsvc_quant_train_args;
 size_t gsvc_quant_train_workspace_bytes(int num_points);
 int gsvc_quant_train_step(const gsvc_quant_train_args *args);
